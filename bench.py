@@ -26,6 +26,9 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
+DUMP_MAX_VALUES = 1 << 21  # --dump-outputs: values per array (float64: 16 MB; with sample_index.npy at most ~32 MB in all)
+DUMP_SEED = 0xD0D0
+DUMP_NAMES = ("sample_index", "distance", "similarity", "filter_count", "filter_index", "filter_score", "topk_distance", "topk_index")
 
 
 def parse():
@@ -82,7 +85,58 @@ def parse():
                          "box; N = 1), else the committed counters of profiles/traffic.json marked as such; off: only the committed file; auto: on for "
                          "workloads of >= 10 M candidates outside the extra legs")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU time of the baseline sample")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (rank 0's view) as DIR/<name>.npy in float64: every value, or a "
+                         "fixed seeded sample of candidates when there are more than %d (sample_index.npy says which); the inputs are the same on every "
+                         "run with the same arguments, so two builds can be compared output for output" % DUMP_MAX_VALUES)
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1 (the number of timed steps)")
+    return args
+
+
+def dump_outputs(path, out=None, filt=None, topk=None, is_f64=False):
+    """--dump-outputs: what the last timed step handed its caller, as float64 .npy files under `path` (u32 results keep their None =
+    0xFFFFFFFF, exactly).  out: the per-candidate results [queries, candidates] -- all of them, or the same seeded sample of candidates
+    on every run (sample_index.npy); filt: the (index, score) pairs of the filter call and their count; topk: the merged top-k keys
+    (distance << 32 | index), best first, empty entries dropped.  Returns {name: shape}."""
+    import torch
+
+    def host(t):
+        a = t.cpu().numpy()
+        return a.astype(np.float64) if is_f64 else a.view(np.uint32).astype(np.float64)
+
+    arrays = {}
+    if out is not None:
+        nq, n_out = out.shape
+        per = max(1, DUMP_MAX_VALUES // nq)
+        if n_out > per:
+            pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n_out, per, replace=False))
+            arrays["sample_index"] = pick.astype(np.float64)
+            out = out[:, torch.from_numpy(pick.astype(np.int64)).to(out.device)]
+        arrays["similarity" if is_f64 else "distance"] = host(out)
+    if filt is not None:
+        count = int(filt["count"].value)
+        m = min(count, filt["idx"].numel())
+        idx, val = filt["idx"][:m], filt["val"][:m]
+        if m > DUMP_MAX_VALUES:
+            pick = torch.from_numpy(np.sort(np.random.default_rng(DUMP_SEED).choice(m, DUMP_MAX_VALUES, replace=False)).astype(np.int64)).to(idx.device)
+            idx, val = idx[pick], val[pick]
+        arrays["filter_count"] = np.array([count], dtype=np.float64)
+        arrays["filter_index"] = idx.cpu().numpy().astype(np.float64)
+        arrays["filter_score"] = host(val)
+    if topk is not None:
+        keys = topk.cpu().numpy()
+        keys = keys[(keys != -1) & (keys != 2**63 - 1)]
+        arrays["topk_distance"] = (keys >> 32).astype(np.float64)
+        arrays["topk_index"] = (keys & 0xFFFFFFFF).astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name in DUMP_NAMES:  # (none left over from an earlier run of another shape)
+        if name not in arrays and os.path.exists(os.path.join(path, name + ".npy")):
+            os.remove(os.path.join(path, name + ".npy"))
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def spawn_ranks(n: int) -> int:
@@ -424,6 +478,9 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:  # (before anything else runs a step: the clock sampling below overwrites the outputs)
+        dumped = dump_outputs(args.dump_outputs, out=None if filt is not None or (args.mode != "many") else out.view(nq, n_out), filt=filt,
+                              topk=last_topk[0], is_f64=is_f64)
 
     kernel_ms = ev0.elapsed_time(ev1) / args.steps  # average launch duration: HIP events on the launch stream over the timed region
     if world > 1 or force_dist:
@@ -539,6 +596,7 @@ def main():
             "settle_steps": settle_steps,
             "first_call_ms": round(first_call_ms, 3),
             **({"test_backend": "gloo: ranks share one GPU, NOT a measurement"} if test_gloo else {}),
+            **({"dumped_outputs": dumped} if args.dump_outputs else {}),
         },
         "roofline": {
             "bound": "hbm",
@@ -899,9 +957,9 @@ def traffic_in_run(args, kernel_ms):
     exe = shutil.which("rocprofv3") or ("/opt/rocm/bin/rocprofv3" if os.path.exists("/opt/rocm/bin/rocprofv3") else None)
     if exe is None or os.environ.get("RF_BENCH_IN_PMC") == "1" or args.gpus != 1:
         return None
-    flags = [a for a in sys.argv[1:]]
+    flags = [a for a in sys.argv[1:] if not a.startswith("--dump-outputs=")]
     for drop, has_val in (("--steps", True), ("--warmup", True), ("--extras", True), ("--settle-ms", True), ("--cpu-seconds", True), ("--traffic", True),
-                          ("--no-cpu-baseline", False)):
+                          ("--dump-outputs", True), ("--no-cpu-baseline", False)):
         while drop in flags:
             i = flags.index(drop)
             del flags[i : i + (2 if has_val else 1)]

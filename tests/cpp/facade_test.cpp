@@ -61,11 +61,11 @@ int main(int argc, char** argv)
         Corpus wide(std::vector<std::u32string_view>{U"\u041f\u0435\u0442\u0440\u0443\u043d\u043a\u043e", U"\u0418\u0432\u0430\u043d", U"plain"});
         auto d = ivanko.distance_many(wide);
         EXPECT(*d[0] == 5 && *d[1] == 2 && *d[2] == 6);
-        wide.save("/tmp/rf_facade_test.rfc");
-        Corpus again = Corpus::load("/tmp/rf_facade_test.rfc");
+        wide.save("rf_facade_test.rfc");
+        Corpus again = Corpus::load("rf_facade_test.rfc");
         auto d2 = ivanko.distance_many(again);
         EXPECT(*d2[0] == 5 && *d2[1] == 2 && *d2[2] == 6);
-        std::remove("/tmp/rf_facade_test.rfc");
+        std::remove("rf_facade_test.rfc");
     }
     EXPECT(distance::indel::distance("lewenstein", "levenshtein") == 3);
     EXPECT(distance::lcs_seq::similarity("lewenstein", "levenshtein") == 9);

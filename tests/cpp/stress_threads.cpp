@@ -359,7 +359,7 @@ int main(int argc, char** argv)
             rf_comparator* cc = nullptr;
             CHECK(rf_comparator_new(RF_LEVENSHTEIN, d.q64.data(), d.q64.size(), &cc));
             std::vector<uint32_t> out(rf_corpus_count(c.ragged) + 1, 0);
-            CHECK(rf_stream_many_u32(cc, "/tmp/rf_stress_ragged.rfc", RF_OP_DISTANCE, &none, out.data(), out.size(), 32u << 20, 0));
+            CHECK(rf_stream_many_u32(cc, "rf_stress_ragged.rfc", RF_OP_DISTANCE, &none, out.data(), out.size(), 32u << 20, 0));
             rf_comparator_free(cc);
             Result r((out.size() + 1) / 2, 0);
             memcpy(r.data(), out.data(), out.size() * 4);
@@ -377,7 +377,7 @@ int main(int argc, char** argv)
     std::vector<Result> expect;
     {
         Corpora ref = pack(d);
-        CHECK(rf_corpus_save(ref.ragged, "/tmp/rf_stress_ragged.rfc"));
+        CHECK(rf_corpus_save(ref.ragged, "rf_stress_ragged.rfc"));
         for (auto& j : jobs) expect.push_back(j(ref, nullptr));
         rf_corpus_free(ref.uniform);
         rf_corpus_free(ref.ragged);
@@ -438,7 +438,7 @@ int main(int argc, char** argv)
     rf_corpus_free(shared.ragged);
     rf_corpus_free(shared.wide);
     rf_corpus_free(shared.small);
-    remove("/tmp/rf_stress_ragged.rfc");
+    remove("rf_stress_ragged.rfc");
     printf("stress_threads: %d threads x 3 x %zu jobs, %d mismatches\n", kThreads, jobs.size(), bad.load());
     return bad.load() ? 1 : 0;
 }

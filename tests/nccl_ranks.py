@@ -11,8 +11,8 @@ only exchange on the path, the k-entry all-gather + merge, through each of its f
 and rank 0 checks all of them against ONE scan of the whole corpus in its own process.  Prints one JSON line on rank 0.
 
 RF_TEST_BACKEND=gloo is the single-GPU stand-in (all ranks share GPU 0, forms 3 and 4 are skipped: RCCL refuses two ranks on one
-device): it keeps this script exercised on the 1-GPU boxes; tests/test_gpu_parity.py runs the nccl form whenever the box has
->= 2 GPUs.
+device): it keeps the multi-rank logic exercised on the 1-GPU boxes; tests/test_gpu_parity.py runs the nccl form with 2 ranks whenever
+the box has >= 2 GPUs, and with 1 rank (all four forms, one-rank communicators) otherwise.
 """
 import ctypes as C
 import glob

@@ -22,13 +22,13 @@ def _build(tmp_path):
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
 def test_cpp_facade_compiles_and_runs_cpu(tmp_path):
-    r = subprocess.run([_build(tmp_path)], capture_output=True, text=True)
+    r = subprocess.run([_build(tmp_path)], capture_output=True, text=True, cwd=tmp_path)
     assert r.returncode == 0, r.stdout + r.stderr
 
 
 @pytest.mark.gpu
 def test_cpp_facade_on_gpu(tmp_path):
-    r = subprocess.run([_build(tmp_path), "gpu"], capture_output=True, text=True)
+    r = subprocess.run([_build(tmp_path), "gpu"], capture_output=True, text=True, cwd=tmp_path)  # (its save / load round trip writes there)
     assert r.returncode == 0 and "facade ok (gpu)" in r.stdout, r.stdout + r.stderr
 
 
@@ -46,5 +46,5 @@ def test_cpp_host_threads_stress_on_gpu(tmp_path):
     subprocess.run([hipcc, "-O1", "-std=c++17", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "stress_threads.cpp"), "-o", exe,
                     "-L", libdir, "-lrfgpu", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib", "-lpthread"], check=True, capture_output=True)
     for _ in range(3):
-        r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+        r = subprocess.run([exe], capture_output=True, text=True, timeout=600, cwd=tmp_path)  # (the streamed-scan job's corpus file goes there)
         assert r.returncode == 0 and ", 0 mismatches" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]

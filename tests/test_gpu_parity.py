@@ -1703,8 +1703,9 @@ def test_bench_gpus_flag_spawns_its_own_ranks():
 
 def test_bench_c5_preset_same_answer_for_every_world_size():
     """--config c5 (BASELINE.json configs[4] scaled down): ONE logical corpus split over the ranks, cutoff 3, top-16,
-    gather + merge every step.  World sizes 1 and 2 must return the same merged top-k (checksum), equal to the oracle's
-    ranking of the planted near-duplicates; the N=1 line goes through the RCCL collective."""
+    gather + merge every step.  World sizes 1, 2 and 4 must return the same merged top-k (checksum), equal to the oracle's
+    ranking of the planted near-duplicates, and so must the 8 shards of configs[4] scanned one by one and merged here;
+    the N=1 line goes through the RCCL collective."""
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -1724,11 +1725,34 @@ def test_bench_c5_preset_same_answer_for_every_world_size():
         dd = _bench_json(base + ["--shard", "dealt"] + (["--gpus", "2"] if gpus == 2 else []), dict(env, RF_BENCH_BACKEND="gloo") if gpus == 2 else env)
         assert dd["n_gpus"] == gpus and dd["parity"]["mismatches"] == 0 and "shard_ragged" in dd["config"]["parallelism"]
         assert dd["config"]["topk_checksum"] == d1["config"]["topk_checksum"] and dd["config"]["topk_best"] == d1["config"]["topk_best"]
-    # the real rank count of configs[4]: 8 ranks (sharing this box's one GPU, exchange over gloo) cut the same logical corpus
-    # into 8 shards with 8 index bases and must merge to the same keys
-    d8 = _bench_json(base + ["--gpus", "8"], dict(env, RF_BENCH_BACKEND="gloo"))
-    assert d8["n_gpus"] == 8 and d8["config"]["ranks_joined"] == 8 and d8["parity"]["mismatches"] == 0
-    assert d8["config"]["topk_checksum"] == d1["config"]["topk_checksum"] and d8["config"]["topk_best"] == d1["config"]["topk_best"]
+    # more ranks than two: 4 ranks (sharing this box's one GPU, exchange over gloo) cut the same logical corpus into 4 shards with 4 index
+    # bases and must merge to the same keys.  (Not 8 processes: with this one, no more than 6 processes may hold a shared GPU at once.)
+    d4 = _bench_json(base + ["--gpus", "4"], dict(env, RF_BENCH_BACKEND="gloo"))
+    assert d4["n_gpus"] == 4 and d4["config"]["ranks_joined"] == 4 and d4["parity"]["mismatches"] == 0
+    assert d4["config"]["topk_checksum"] == d1["config"]["topk_checksum"] and d4["config"]["topk_best"] == d1["config"]["topk_best"]
+    # the real rank count of configs[4]: 8 shards with 8 index bases, each scanned here the way a c5 rank scans its own
+    # (the rows of parallel.shard_range's slice, top-16 keys at the slice's index base, cutoff 3), merged by the device merge: the same keys
+    import torch
+
+    from rapidfuzz_rs_amd import parallel
+
+    dev = torch.device("cuda", 0)
+    total, world, k = 3_000_000, 8, 16
+    q = synth.query(64, 0xC0FFEE05)
+    scorer = rf.distance.levenshtein.BatchComparator(q)
+    gathered = torch.empty(k * world, dtype=torch.int64, device=dev)
+    shards = []  # (kept until the merge has run: the scans are asynchronous)
+    for rank in range(world):
+        lo, hi = parallel.shard_range(total, rank, world)
+        shards.append(rf.Corpus.from_device_rows(synth.rows_device_range(lo, hi, 64, seed=0xC0FFEE05, device=dev, q=q, plant_every=50_000)))
+        scorer.topk_keys_device(shards[-1], k, gathered[rank * k : (rank + 1) * k], N.OP_DISTANCE, rf.Args().score_cutoff(3), index_base=lo)
+    merged = parallel.merge_keys_device(gathered, k, torch.empty(k, dtype=torch.int64, device=dev))
+    torch.cuda.synchronize()
+    import zlib
+
+    keys8 = sorted(int(x) for x in merged.cpu().tolist() if x not in (-1, 2**63 - 1))
+    assert len(keys8) == d1["config"]["topk_found"] and [[x >> 32, x & 0xFFFFFFFF] for x in keys8[:4]] == d1["config"]["topk_best"]
+    assert zlib.crc32(np.array(keys8, dtype=np.uint64).tobytes()) == d1["config"]["topk_checksum"]
 
 
 @pytest.mark.parametrize("k", [1, 2, 16])
@@ -2878,30 +2902,31 @@ def test_ranks_script_two_ranks_sharing_one_gpu_over_gloo():
 
 
 def test_real_ranks_over_rccl_when_the_box_has_two_gpus():
-    """>= 2 GPUs: one rank per GPU over RCCL -- every form of the k-entry exchange (torch.distributed collectives
-    and the raw-ncclComm_t entry points rf_topk_allgather_merge[_entries]) against one scan of the whole corpus, then bench.py's own
-    multi-GPU paths: `--gpus 2` (weak scaling, exchange self-check) and `--config c5` at world sizes 1 and 2 to the same checksum.
-    Skips on the 1-GPU boxes of this pool; the first multi-GPU lease runs it."""
+    """One rank per GPU over RCCL, 2 ranks when the box has >= 2 GPUs -- every form of the k-entry exchange
+    (torch.distributed collectives and the raw-ncclComm_t entry points rf_topk_allgather_merge[_entries]) against one scan of the whole
+    corpus, then bench.py's own multi-GPU paths: `--gpus 2` (weak scaling, exchange self-check) and `--config c5` at world sizes 1 and 2
+    to the same checksum.  On a 1-GPU box (RCCL refuses two ranks on one device) the same legs run with ONE real RCCL rank: the script's
+    communicators, bench.py's exchange path forced on at N = 1 (RF_BENCH_FORCE_DIST), and c5 contiguous vs dealt through the collective."""
     import sys
 
     import torch
 
     ngpu = torch.cuda.device_count()
-    if ngpu < 2:
-        pytest.skip(f"needs >= 2 GPUs for real RCCL ranks, this box has {ngpu}")
-    world = 2
+    assert ngpu >= 1, "no GPU visible"
+    world = min(ngpu, 2)
     d = _run_ranks_script(world, {}, 29657)
-    assert d["ok"] and d["backend"] == "nccl" and d["gpus"] == world and d["same_on_every_rank"] and all(d["checks"].values()), d
+    assert d["ok"] and d["backend"] == "nccl" and d["gpus"] == world and d["ranks"] == world and d["same_on_every_rank"] and all(d["checks"].values()), d
     assert {"raw_keys_cut3", "raw_entries_jw"} <= set(d["checks"])
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "RF_BENCH_BACKEND")}
     b = _bench_json([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(world), "--candidates", "2000000", "--steps", "3", "--warmup", "1",
-                     "--no-cpu-baseline"], env)
+                     "--no-cpu-baseline"], dict(env, RF_BENCH_FORCE_DIST="1") if world == 1 else env)
     assert b["n_gpus"] == world and b["config"]["rccl_ranks"] == world and b["config"]["exchange_selfcheck"]["inconsistent"] == 0
     base = [sys.executable, os.path.join(root, "bench.py"), "--config", "c5", "--total-candidates", "6000000", "--plant-every", "50000", "--steps", "3",
             "--warmup", "1", "--cpu-seconds", "0.3"]
     d1 = _bench_json(base, env)
-    d2 = _bench_json(base + ["--gpus", str(world)], env)
+    assert d1["config"]["rccl_ranks"] == 1 and d1["parity"]["mismatches"] == 0
+    d2 = _bench_json(base + (["--gpus", str(world)] if world > 1 else ["--shard", "dealt"]), env)
     assert d2["n_gpus"] == world and d2["config"]["rccl_ranks"] == world and d2["parity"]["mismatches"] == 0
     assert d2["config"]["topk_checksum"] == d1["config"]["topk_checksum"] and d2["config"]["topk_best"] == d1["config"]["topk_best"]
 
