@@ -262,7 +262,8 @@ typedef struct rf_host_layout {
     uint32_t n_tiles, identity;
     uint8_t sigma[256];    /* symbol renaming: the payload stores sigma[c] for candidate byte c (a permutation that
                               spreads this corpus' frequent symbols over distinct LDS banks) */
-    uint32_t n_exact;      /* tiles [0, n_exact) hold 64 candidates of one length each (whole multiples of 64 per length) */
+    uint32_t n_exact;      /* tiles [0, n_exact) hold 64 candidates of one length each (whole multiples of 64 per length; under RF_NO_MIXED_TILES every
+                              length's candidates, its last tile ending in padding lanes) */
     uint32_t n_mixed;      /* the leftovers of every length, sorted by length, share n_mixed MIXED payload blocks of 64 lanes;
                               tiles [n_exact, n_tiles) are the one-length views of those blocks (one per distinct length in a
                               block, same tile_off, orig = 0xFFFFFFFF for the lanes of other lengths) */

@@ -306,6 +306,7 @@ rf_status make_effective(const rf_comparator* c_in, const rf_corpus* corpus, hip
     v.d_orig = corpus->d_orig;
     v.n_tiles = corpus->n_tiles;
     v.n_exact = corpus->n_exact;
+    v.exact_dense = corpus->exact_dense;
     v.n_mixed = corpus->n_mixed;
     v.d_mixed = corpus->d_mixed;
     v.d_mixed_len = corpus->d_mixed_len;
@@ -407,6 +408,7 @@ struct HostLayout {
     size_t packed_size = 0;
     std::vector<TileDesc> tiles;   // [exact tiles, ascending length | virtual tiles of the mixed section, ascending length]
     uint32_t n_exact = 0;          // tiles [0, n_exact) are exact, [n_exact, size) virtual
+    bool exact_dense = true;       // no padding lane in tiles [0, n_exact) (rf_corpus::exact_dense)
     std::vector<uint32_t> orig;    // slot -> original index (kPad = padding lane); empty when identity
     std::vector<MixedDesc> mixed;  // the mixed section as the scans see it
     std::vector<uint32_t> mixed_len, mixed_orig;  // 64 per mixed tile: lane -> length / original index (kPad = no candidate)
@@ -473,6 +475,7 @@ static rf_status build_layout(const uint8_t* bytes, const uint64_t* offsets, siz
         const bool all = L->identity || no_mixed;
         const uint64_t nt = all ? (g.count + kWave - 1) / kWave : g.count / kWave;
         g.in_exact = all ? g.count : nt * kWave;
+        if (g.in_exact % kWave) L->exact_dense = false;  // (this length's last exact tile ends in padding lanes)
         g.slot0 = slots;
         g.off0 = data_bytes;
         for (uint64_t t = 0; t < nt; ++t) {
@@ -696,6 +699,7 @@ static rf_status corpus_from_layout(const HostLayout& L, size_t n, int device, r
     c->payload_bytes = L.payload;
     c->n_tiles = (uint32_t)L.tiles.size();
     c->n_exact = L.n_exact;
+    c->exact_dense = L.exact_dense;
     c->n_mixed = (uint32_t)L.mixed.size();
     c->mixed = L.mixed;
     c->max_len = L.max_len;
@@ -909,11 +913,13 @@ static rf_status pack_ragged_device(const uint8_t* bytes, const uint64_t* offset
     const bool identity = groups.size() <= 1 && tile_bytes(max_len) <= 0xFFFFFFFFull;
     static const bool no_mixed = getenv("RF_NO_MIXED_TILES") != nullptr;
     std::vector<TileDesc> tiles;
+    bool exact_dense = true;
     uint64_t slots = 0, data_bytes = 0, pool_n = 0;
     for (Group& g : groups) {
         const bool all = identity || no_mixed;
         const uint64_t nt = all ? (g.count + kWave - 1) / kWave : g.count / kWave;
         g.in_exact = all ? g.count : nt * kWave;
+        if (g.in_exact % kWave) exact_dense = false;
         g.slot0 = slots;
         g.off0 = data_bytes;
         for (uint64_t t = 0; t < nt; ++t) {
@@ -969,6 +975,7 @@ static rf_status pack_ragged_device(const uint8_t* bytes, const uint64_t* offset
     c->payload_bytes = span;
     c->n_tiles = (uint32_t)tiles.size();
     c->n_exact = n_exact;
+    c->exact_dense = exact_dense;
     c->n_mixed = (uint32_t)mixed.size();
     c->mixed = mixed;
     c->max_len = max_len;

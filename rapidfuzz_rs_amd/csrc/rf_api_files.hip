@@ -301,6 +301,8 @@ static rf_status load_meta(FILE* f, const FileHeader& h, rf_corpus* c, std::vect
             ++real;
         }
         if (real != c->n) return bad("slot map does not cover every candidate");
+        // the file does not say whether it was packed under RF_NO_MIXED_TILES: the slot map does (a padding lane below n_exact x 64)
+        c->exact_dense = std::find(orig->begin(), orig->begin() + (size_t)c->n_exact * kWave, kPad) == orig->begin() + (size_t)c->n_exact * kWave;
     }
     for (const auto& kv : c->alphabet)
         if (kv.second >= kOverflowId) return bad("alphabet id");

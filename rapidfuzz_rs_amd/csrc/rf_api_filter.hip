@@ -335,7 +335,8 @@ static rf_status run_filter(const rf_comparator* c, const rf_corpus* corpus, rf_
         }
         if (const rf_status rs = run_many(c, corpus, op, &a, d_tmp, RF_MEM_DEVICE, stream, f64_out); rs != RF_OK) return rs;
         uint32_t h[5] = {0, 0, 1, 0, 0};
-        const uint32_t exact_slots = corpus->n_exact * (uint32_t)kWave;
+        // the count reads the slot map only from here on: the exact tiles, unless one of them ends in padding lanes (RF_NO_MIXED_TILES)
+        const uint32_t exact_slots = corpus->exact_dense ? corpus->n_exact * (uint32_t)kWave : 0u;
         if (const rf_status rs = general(static_cast<const uint8_t*>(d_tmp) + w0 * elem, slots ? corpus->d_orig + w0 : nullptr,
                                          slots ? (uint32_t)(exact_slots > w0 ? exact_slots - w0 : 0) : 0u, (uint32_t)(w1 - w0), nullptr, !slots, nullptr, h, nullptr);
             rs != RF_OK)

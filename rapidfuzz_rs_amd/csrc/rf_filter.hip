@@ -26,7 +26,7 @@ __device__ __forceinline__ bool some(uint32_t v) { return v != RF_NONE_U32; }
 __device__ __forceinline__ bool some(double v) { return v == v; }
 
 // entries [0, m): m = min(m_bound, *m_dev) when m_dev is given.  map (nullable): entry -> index, kPad = not a candidate; entries below map_from are known to be
-// candidates (the exact tiles of a bucketed corpus have no padding lane), so the COUNT need not read the map there.
+// candidates (the exact tiles of a bucketed corpus, when none of them ends in padding lanes: rf_corpus::exact_dense), so the COUNT need not read the map there.
 template <class T>
 __global__ __launch_bounds__(256) void filter_count_kernel(const T* __restrict__ val, const uint32_t* __restrict__ map, uint32_t map_from, uint32_t m_bound,
                                                            const uint32_t* __restrict__ m_dev, uint32_t n_seg, uint32_t* __restrict__ seg_cnt)

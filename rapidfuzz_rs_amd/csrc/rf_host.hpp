@@ -103,6 +103,7 @@ struct rf_corpus {
     mutable uint32_t gather_runs = 0, gather_rows = 0;
     uint32_t n_tiles = 0;        // exact tiles, then the virtual (one-length) views of the mixed section
     uint32_t n_exact = 0;        // tiles [0, n_exact) are exact-length tiles; [n_exact, n_tiles) virtual views (HostLayout)
+    bool exact_dense = false;    // no padding lane in tiles [0, n_exact) (false under RF_NO_MIXED_TILES when a length's count is not a multiple of 64: its last tile is partial)
     // the mixed section as the Levenshtein / LCS / OSA scans see it: one tile of 64 leftovers with per-lane lengths
     uint32_t n_mixed = 0;
     MixedDesc* d_mixed = nullptr;

@@ -108,6 +108,36 @@ def test_host_layout_roundtrip(n, max_len):
         assert ne == int((counts // 64).sum()) and lay["n_mixed"] == -(-int((counts % 64).sum()) // 64)
 
 
+def test_host_layout_without_mixed_tiles_pads_every_length(tmp_path):
+    """RF_NO_MIXED_TILES (read once per process: a child): no mixed section, every length padded to whole tiles -- so below n_exact x 64 the slot map holds
+    padding exactly at the end of each length's last tile.  tests/test_gpu_layouts.py relies on this layout for its no_mixed legs."""
+    import subprocess
+    import sys
+
+    data, offsets = synth.ragged_host(5000, 70, seed=19, min_len=1)
+    np.save(tmp_path / "data.npy", data)
+    np.save(tmp_path / "offsets.npy", offsets)
+    child = ("import sys, numpy as np; sys.path.insert(0, %r); import rapidfuzz_rs_amd as rf; "
+             "lay = rf.host_layout(np.load(%r), np.load(%r)); "
+             "np.savez(%r, orig=lay['orig'], tile_len=lay['tile_len'], n_exact=lay['n_exact'], n_mixed=lay['n_mixed'])") % (
+                 ROOT, str(tmp_path / "data.npy"), str(tmp_path / "offsets.npy"), str(tmp_path / "lay.npz"))
+    r = subprocess.run([sys.executable, "-c", child], capture_output=True, text=True, cwd=ROOT, env=dict(os.environ, RF_NO_MIXED_TILES="1"), timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lay = np.load(tmp_path / "lay.npz")
+    counts = np.bincount((offsets[1:] - offsets[:-1]).astype(np.int64))
+    assert int(lay["n_mixed"]) == 0 and int(lay["n_exact"]) == len(lay["tile_len"]) == int((-(-counts // 64)).sum())
+    assert any(c % 64 for c in counts)  # (some length ends in a partial tile: what the test is about)
+    pad = np.zeros(int(lay["n_exact"]) * 64, dtype=bool)
+    at = 0
+    for ln, c in enumerate(counts):
+        t = -(-int(c) // 64)
+        assert (lay["tile_len"][at // 64: at // 64 + t] == ln).all()
+        pad[at + int(c): at + 64 * t] = True
+        at += 64 * t
+    assert len(lay["orig"]) == len(pad) and np.array_equal(lay["orig"] == 0xFFFFFFFF, pad)
+    assert np.array_equal(np.sort(lay["orig"][~pad]), np.arange(5000, dtype=np.uint32))
+
+
 def test_host_layout_distinct_lengths_pack_to_their_payload():
     """VERDICT r1 missing #5: exact-length tiles cost up to 64x on corpora with many distinct lengths.  10 000 candidates of
     10 000 different lengths now share mixed tiles: the packed form stays within 2x of the payload (round 1: 64x)."""

@@ -247,6 +247,10 @@ def test_filter_and_slot_order_on_a_length_bucketed_corpus():
         assert len(_same(back, exp)) == 0, ("slot order", metric, op, kw)
         if kw:
             _filter_check(bc, ob, op, corpus, exp, **kw)
+    # no cutoff: every candidate is a pair, the padding lanes of the mixed-tile views none (the count reads their slot map)
+    bc, ob = GPU["indel"].BatchComparator(q), ORA["indel"].BatchComparator(q)
+    _filter_check(bc, ob, N.OP_DISTANCE, corpus, ob.many(N.OP_DISTANCE, data, offsets, nthreads=8))
+    assert bc.last_filter_count == n
     # the query > 64 symbols (multi-word scans) in slot order
     q2 = (q * 3)[:100]
     bc, ob = GPU["levenshtein"].BatchComparator(q2), ORA["levenshtein"].BatchComparator(q2)
@@ -285,7 +289,7 @@ def test_device_packer_equals_the_host_layout_byte_for_byte(shape, tmp_path):
     """rf_corpus_pack does its per-candidate work on the device now (rf_pack_ragged.hip: length keys + histogram, stable radix sort by length,
     one scatter kernel per destination tile).  The layout's specification stays the host packer (rf_corpus_layout_host / build_layout): the same input packed with
     RF_DEVICE_PACK_MIN=0 (host) in a child process and on the device here must SAVE to identical files -- header, length table, tile descriptors, slot map, mixed
-    section, every payload byte (file format unchanged) -- and scan to the oracle's values."""
+    section, every payload byte (file format unchanged) -- and scan to the oracle's values; the same for the two packers under RF_NO_MIXED_TILES (children)."""
     rng = np.random.default_rng(len(shape))
     n = 300_011
     if shape == "ragged":
@@ -305,23 +309,33 @@ def test_device_packer_equals_the_host_layout_byte_for_byte(shape, tmp_path):
         data = np.concatenate([rng.integers(48, 123, size=12345, dtype=np.uint8), data])
     np.save(tmp_path / "data.npy", data)
     np.save(tmp_path / "offsets.npy", offsets)
-    child = ("import sys, numpy as np; sys.path.insert(0, %r); import rapidfuzz_rs_amd as rf; "
-             "rf.Corpus.from_ragged(np.load(%r), np.load(%r)).save(%r)") % (ROOT, str(tmp_path / "data.npy"), str(tmp_path / "offsets.npy"), str(tmp_path / "host.rfc"))
-    r = subprocess.run([sys.executable, "-c", child], capture_output=True, text=True, cwd=ROOT, env=dict(os.environ, RF_DEVICE_PACK_MIN="0"))
-    assert r.returncode == 0, r.stderr[-2000:]
+    def pack_in_child(name, **env):
+        child = ("import sys, numpy as np; sys.path.insert(0, %r); import rapidfuzz_rs_amd as rf; "
+                 "rf.Corpus.from_ragged(np.load(%r), np.load(%r)).save(%r)") % (ROOT, str(tmp_path / "data.npy"), str(tmp_path / "offsets.npy"), str(tmp_path / name))
+        r = subprocess.run([sys.executable, "-c", child], capture_output=True, text=True, cwd=ROOT, env=dict(os.environ, **env), timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        return open(tmp_path / name, "rb").read()
+
+    def same_bytes(dev_file, host_file, what):
+        assert len(dev_file) == len(host_file), what
+        if dev_file != host_file:
+            a, b = np.frombuffer(dev_file, dtype=np.uint8), np.frombuffer(host_file, dtype=np.uint8)
+            bad = np.nonzero(a != b)[0]
+            raise AssertionError(f"{what}: {len(bad)} bytes differ, first at {bad[:8]}")
+
+    host_file = pack_in_child("host.rfc", RF_DEVICE_PACK_MIN="0")
     corpus = rf.Corpus.from_ragged(data, offsets)
-    dev_file, host_file = _saved(corpus, tmp_path / "dev.rfc"), open(tmp_path / "host.rfc", "rb").read()
-    assert len(dev_file) == len(host_file)
-    if dev_file != host_file:
-        a, b = np.frombuffer(dev_file, dtype=np.uint8), np.frombuffer(host_file, dtype=np.uint8)
-        bad = np.nonzero(a != b)[0]
-        raise AssertionError(f"{len(bad)} bytes differ, first at {bad[:8]}")
+    same_bytes(_saved(corpus, tmp_path / "dev.rfc"), host_file, "default layout")
+    # every length padded to whole tiles (RF_NO_MIXED_TILES, read once per process: both packers in children)
+    same_bytes(pack_in_child("dev_nm.rfc", RF_NO_MIXED_TILES="1"), pack_in_child("host_nm.rfc", RF_NO_MIXED_TILES="1", RF_DEVICE_PACK_MIN="0"), "RF_NO_MIXED_TILES")
+    loaded = rf.Corpus.load(str(tmp_path / "dev_nm.rfc"))
     q = bytes(data[int(offsets[7]): int(offsets[7]) + 40]) or b"abc"
     for metric in ("levenshtein", "indel", "jaro_winkler"):
         op = N.OP_SIMILARITY if metric == "jaro_winkler" else N.OP_DISTANCE
-        got = GPU[metric].BatchComparator(q).many(op, corpus)
         exp = ORA[metric].BatchComparator(q).many(op, data, offsets, nthreads=8)
-        assert len(_same(got, exp)) == 0, metric
+        for c in (corpus, loaded):
+            got = GPU[metric].BatchComparator(q).many(op, c)
+            assert len(_same(got, exp)) == 0, metric
 
 
 @pytest.mark.parametrize("seed", range(int(os.environ.get("RF_FUZZ_SEEDS", "16"))))

@@ -31,8 +31,10 @@ def _expect_u32(ora_out):
     return np.where(ora_out == U64MAX, NONE32, ora_out.astype(np.uint32))
 
 
-def _check_many(metric, q, data, offsets, op, **kw):
-    corpus = rf.Corpus.from_ragged(data, offsets)
+def _check_many(metric, q, data, offsets, op, corpus=None, **kw):
+    """`corpus`: the packed form of data / offsets to scan (default: packed here)"""
+    if corpus is None:
+        corpus = rf.Corpus.from_ragged(data, offsets)
     got = GPU[metric].BatchComparator(q).many(OPS[op], corpus, **kw)
     exp = ORA[metric].BatchComparator(q).many(OPS[op], data, offsets, nthreads=8, **kw)
     if metric == "levenshtein" and op == "similarity" and kw.get("score_cutoff") is not None:
