@@ -1312,27 +1312,13 @@ void rf_corpus_free(rf_corpus* c)
     if (c->d_window_table) (void)hipFree(c->d_window_table);
     if (c->d_slot_off16) (void)hipFree(c->d_slot_off16);
     if (c->d_len_of) (void)hipFree(c->d_len_of);
-    for (const rf_corpus::GatherTmp& t : c->gather_tmp) {
-        if (t.done) (void)hipEventDestroy(t.done);
-        (void)hipFree(t.ptr);
-    }
-    for (const rf_corpus::TileList& t : c->tile_lists) {
-        (void)hipFree(t.ptr);
-        (void)hipEventDestroy(t.done);
-        if (t.band_report) (void)hipHostFree(const_cast<uint32_t*>(t.band_report));
-    }
     if (c->d_mixed) (void)hipFree(c->d_mixed);
     if (c->d_mixed_len) (void)hipFree(c->d_mixed_len);
     if (c->d_mixed_orig) (void)hipFree(c->d_mixed_orig);
     if (c->d_sigma) (void)hipFree(c->d_sigma);
     if (c->d_raw) (void)hipFree(c->d_raw);
     if (c->d_sigma_identity) (void)hipFree(c->d_sigma_identity);
-    for (auto& kv : c->topk_scratch) {
-        (void)hipFree(kv.second.cand);
-        if (kv.second.scores) (void)hipFree(kv.second.scores);
-        if (kv.second.done) (void)hipEventDestroy(kv.second.done);
-    }
-    delete c;
+    delete c;  // (and with it the per-stream caches)
 }
 
 size_t rf_corpus_count(const rf_corpus* c) { return c->n; }
@@ -1353,18 +1339,8 @@ uint64_t rf_corpus_device_bytes(const rf_corpus* c)
         if (c->d_window_table) aux += (uint64_t)c->gather_rows * c->gather_runs * sizeof(uint32_t);
         if (c->d_slot_off16) aux += (uint64_t)c->n_slots * sizeof(uint16_t);
         if (c->d_len_of) aux += (uint64_t)c->n * sizeof(uint32_t);
-        for (const auto& kv : c->topk_scratch)  // (candidate ways + root table + bound line + control block, and the score vector if any)
-            aux += (uint64_t)64 * kv.second.seg_cap * sizeof(uint64_t) + 64 * kWave * sizeof(uint64_t) + 128 + 65 * 128 + (uint64_t)kv.second.scores_cap * sizeof(uint32_t);
     }
-    {
-        std::lock_guard<std::mutex> lock(c->gather_enqueue_mu);
-        for (const rf_corpus::GatherTmp& t : c->gather_tmp) aux += t.bytes;
-    }
-    {
-        std::lock_guard<std::mutex> lock(c->filter_enqueue_mu);
-        aux += (uint64_t)c->tile_lists.size() * (9 * (uint64_t)c->n_tiles + 12 * 16384 + 64) * sizeof(uint32_t);  // (rf_api_scan.hip tile_list_words: the lane lists' 16-byte entries since round 6)
-    }
-    return c->device_bytes + aux;
+    return c->device_bytes + aux + c->topk_scratch.bytes() + c->gather_tmp.bytes() + c->tile_lists.bytes();
 }
 int rf_corpus_device(const rf_corpus* c) { return c->device; }
 size_t rf_corpus_alphabet_size(const rf_corpus* c, size_t* overflow_symbols)

@@ -94,7 +94,7 @@ bool await_slot(ResultSlot& slot, hipStream_t st, uint32_t h[3])
 // The first road.  Returns RF_OK with *took = false when the launch would not go through the lane compaction (the caller then takes the second road).
 // On success: lane_val / lane_idx hold the survivors' results, *d_total (device) their number, cap2 the room they had.
 static rf_status filter_fast(const rf_comparator* c_in, const rf_corpus* corpus_in, rf_op op, const rf_args* args, bool f64_out, uint64_t capacity, hipStream_t st,
-                             ScratchSet& sc, bool* took, void** lane_val, uint32_t** lane_idx, uint32_t** d_total, uint32_t* cap2_out, std::unique_lock<std::mutex>* held)
+                             ScratchSet& sc, bool* took, void** lane_val, uint32_t** lane_idx, uint32_t** d_total, uint32_t* cap2_out, rf_corpus::TileLease* held)
 {
     *took = false;
     static const bool lane_compact = [] { const char* e = getenv("RF_LANE_COMPACT"); return !e || atoi(e) != 0; }();
@@ -110,9 +110,9 @@ static rf_status filter_fast(const rf_comparator* c_in, const rf_corpus* corpus_
     if (!p.heads8) return RF_OK;
     p.heads6 = corpus_head6_plane(corpus, st);
     plan_band_filter(c, corpus, op, f64_out, &p, corpus->uniform_len);
-    std::unique_lock<std::mutex> filter_lock(corpus->filter_enqueue_mu);
-    p.tile_list_buf = corpus_tile_list(corpus, st);
-    corpus_lane_buffers(corpus, &p);
+    rf_corpus::TileLease list = corpus->tile_list_lease(st);
+    p.tile_list_buf = list ? list->ptr : nullptr;
+    p.lane_list = list ? 1u : 0u;
     if (!p.lane_list || !head_two_pass_applies(raw, p)) return RF_OK;
     // room for the survivors of the first pass (NOT the passers: a corpus that shares prefixes with the query has many more survivors than matches); a call whose
     // survivors do not fit takes the second road afterwards -- correct either way
@@ -131,7 +131,7 @@ static rf_status filter_fast(const rf_comparator* c_in, const rf_corpus* corpus_
     static const bool trace_plan = getenv("RF_TRACE_PLAN") != nullptr;
     if (trace_plan) std::fprintf(stderr, "[rf plan] filter: lane compaction, first_check=%u head_need=%u head_k=%u room for %u survivors\n", p.first_check, p.head_need, p.head_k, cap2);
     const hipError_t e = launch_scan(raw, p, st, nullptr);
-    *held = std::move(filter_lock);
+    *held = std::move(list);
     if (e != hipSuccess) {
         set_error(std::string("filter scan launch: ") + hipGetErrorString(e));
         return RF_ERR_HIP;
@@ -275,14 +275,11 @@ static rf_status run_filter(const rf_comparator* c, const rf_corpus* corpus, rf_
         bool took = false;
         void* lane_val = nullptr;
         uint32_t *lane_idx = nullptr, *d_total = nullptr, cap2 = 0;
-        std::unique_lock<std::mutex> held;
+        rf_corpus::TileLease held;
         if (const rf_status rs = filter_fast(c, corpus, op, args, f64_out, capacity, st, sc, &took, &lane_val, &lane_idx, &d_total, &cap2, &held); rs != RF_OK) return rs;
         if (took) {
             uint32_t h[5] = {0, 0, 1, 0, 0};
-            auto release = [&]() {  // everything that reads the tile-list buffer has been enqueued
-                corpus_tile_list_done(corpus, st);
-                held.unlock();
-            };
+            auto release = [&]() { held.release(); };  // everything that reads the tile-list buffer has been enqueued
             second_road = false;
             void* ws = cap ? select_workspace(corpus->device) : nullptr;
             if (ws) {

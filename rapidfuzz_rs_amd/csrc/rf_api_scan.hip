@@ -570,62 +570,6 @@ void plan_band_filter(const rf_comparator* c, const rf_corpus* corpus, rf_op op,
     p->head_k = (uint32_t)K;
 }
 
-// words of a tile-list buffer: round 5's layout (packed count, <= 16 K per-wavefront counts and offsets, their segments -- n_tiles + 2 per wavefront of rounding --, the
-// packed list) needs 2 n_tiles + 5 x 16384; the lane lists (rf_scan.hip lane_list_pack_kernel: 16-byte entries in the segments and in the packed list) four times the entries
-static size_t tile_list_words(uint32_t n_tiles) { return 9 * (size_t)n_tiles + 12 * 16384 + 64; }  // (the last 4 words: launch_band's count of hand-over candidates, zero between launches)  // (+ one word per dense tile: lane_list_pack_kernel's first[])
-// the buffer serves the lane compaction (every buffer corpus_tile_list hands out does)
-void corpus_lane_buffers(const rf_corpus* corpus, ScanParams* p)
-{
-    (void)corpus;
-    p->lane_list = p->tile_list_buf ? 1u : 0u;
-}
-
-// this stream's tile list for head_filter_kernel (the caller holds corpus->filter_enqueue_mu); nullptr = none to be had, the
-// scan then filters inside the cutoff kernel
-uint32_t* corpus_tile_list(const rf_corpus* corpus, hipStream_t st)
-{
-    for (size_t i = 0; i < corpus->tile_lists.size(); ++i)
-        if (corpus->tile_lists[i].stream == st) {  // most recently used first
-            const rf_corpus::TileList hit = corpus->tile_lists[i];
-            corpus->tile_lists.erase(corpus->tile_lists.begin() + (long)i);
-            corpus->tile_lists.insert(corpus->tile_lists.begin(), hit);
-            return hit.ptr;
-        }
-    if (corpus->tile_lists.size() >= 4) {
-        // a fifth stream: the least recently used list changes hands instead of the scan silently falling back to the slower
-        // in-kernel filter.  Its old stream's work is waited for first -- rare, and only then.
-        rf_corpus::TileList lru = corpus->tile_lists.back();
-        corpus->tile_lists.pop_back();
-        (void)hipEventSynchronize(lru.done);  // (the event, not the stream handle: that stream may no longer exist)
-        lru.stream = st;
-        corpus->tile_lists.insert(corpus->tile_lists.begin(), lru);
-        return lru.ptr;
-    }
-    uint32_t* ptr = nullptr;
-    if (hipMalloc((void**)&ptr, tile_list_words(corpus->n_tiles) * sizeof(uint32_t)) != hipSuccess) {
-        (void)hipGetLastError();
-        return nullptr;
-    }
-    if (hipMemsetAsync(ptr + tile_list_words(corpus->n_tiles) - 4, 0, 4 * sizeof(uint32_t), st) != hipSuccess) (void)hipGetLastError();
-    hipEvent_t done = nullptr;
-    if (hipEventCreateWithFlags(&done, hipEventDisableTiming) != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipFree(ptr);
-        return nullptr;
-    }
-    corpus->tile_lists.insert(corpus->tile_lists.begin(), {st, ptr, done});
-    return ptr;
-}
-// the scan that walks this stream's list has been enqueued (the caller still holds corpus->filter_enqueue_mu)
-void corpus_tile_list_done(const rf_corpus* corpus, hipStream_t st)
-{
-    for (const rf_corpus::TileList& t : corpus->tile_lists)
-        if (t.stream == st) {
-            (void)hipEventRecord(t.done, st);
-            return;
-        }
-}
-
 // RF_TILE_ORDER (run_many has what it selects): 0 = never by origin, 1 = by origin without the XCD deal, 2 = default, 3 = also the
 // kernels that lose by it
 static int tile_order_knob()
@@ -937,31 +881,17 @@ static rf_status run_many_hinted(const rf_comparator* c_in, const rf_corpus* cor
             p2.tile_begin == p1.tile_begin && p2.tile_end == p1.tile_end) {
             if (const rf_status rs = comparator_device_pm(c, corpus->device, &p1.pm); rs != RF_OK) return rs;
             p2.pm = p1.pm;
-            std::unique_lock<std::mutex> list_lock(corpus->filter_enqueue_mu);
-            uint32_t* buf = corpus_tile_list(corpus, st);
+            rf_corpus::TileLease list = corpus->tile_list_lease(st);
             uint32_t *packed_at = nullptr, *first_at = nullptr;
-            p1.tile_list_buf = buf;
-            bool go = buf != nullptr && band_list_geometry(p1, &packed_at, &first_at);
-            volatile uint32_t* report = nullptr;
-            if (go) {
-                rf_corpus::TileList& tl = corpus->tile_lists.front();  // (corpus_tile_list moved this stream's list to the front)
-                if (!tl.band_report) {
-                    void* hp = nullptr;
-                    if (hipHostMalloc(&hp, 64, hipHostMallocMapped | hipHostMallocPortable) == hipSuccess) {
-                        std::memset(hp, 0, 64);
-                        tl.band_report = static_cast<volatile uint32_t*>(hp);
-                    } else {
-                        (void)hipGetLastError();
-                    }
-                }
-                report = tl.band_report;
-                if (report && report[10] != 0) {  // the last such call on this stream: did its first pass leave more than 30 % of the corpus?
-                    const uint64_t left = report[8], of = report[9];
-                    report[10] = 0;
-                    if (left * 10 > of * 3) {
-                        corpus->hint_trust.store(0, std::memory_order_relaxed);
-                        go = false;
-                    }
+            p1.tile_list_buf = list ? list->ptr : nullptr;
+            bool go = list && band_list_geometry(p1, &packed_at, &first_at);
+            volatile uint32_t* report = go ? list->report() : nullptr;
+            if (report && report[10] != 0) {  // the last such call on this stream: did its first pass leave more than 30 % of the corpus?
+                const uint64_t left = report[8], of = report[9];
+                report[10] = 0;
+                if (left * 10 > of * 3) {
+                    corpus->hint_trust.store(0, std::memory_order_relaxed);
+                    go = false;
                 }
             }
             if (go) {
@@ -973,11 +903,10 @@ static rf_status run_many_hinted(const rf_comparator* c_in, const rf_corpus* cor
                 p2.prefill_none = 0;
                 p2.tile_list = packed_at;
                 p2.lane_first = first_at;
-                p2.tile_list_count = buf;
+                p2.tile_list_count = p1.tile_list_buf;
                 p2.band_report = const_cast<uint32_t*>(report);
                 RF_HIP(launch_sparse_words(p2, st));
-                corpus_tile_list_done(corpus, st);
-                list_lock.unlock();
+                list.release();
                 corpus->hint_trust.store(std::min<uint32_t>(trust + 1, 0x7FFFFFFFu), std::memory_order_relaxed);
                 static const bool trace_lists = getenv("RF_TRACE_PLAN") != nullptr;
                 if (trace_lists) std::fprintf(stderr, "[rf plan] hint lists: k1=%u, the band pass lists what it leaves, %u-word scan over the list\n", k1, p2.words);
@@ -1251,8 +1180,7 @@ rf_status run_many(const rf_comparator* c_in, const rf_corpus* corpus_in, rf_op 
     static const size_t unscatter_min = [] { const char* e = getenv("RF_UNSCATTER_MIN"); return e ? (size_t)atoll(e) : (size_t)1 << 20; }();
     void* d_tmp = nullptr;
     bool tmp_owned = false;                 // d_tmp is this call's own stream-ordered allocation
-    rf_corpus::GatherTmp* kept_tmp = nullptr;  // ... or this kept buffer of the corpus (valid while tmp_lock is held)
-    std::unique_lock<std::mutex> tmp_lock;  // held while a kept temporary's scan + gather are enqueued
+    StreamCache<rf_corpus::GatherTmp>::Lease kept;  // ... or this stream's kept buffer of the corpus; the lease is held while the scan + gather are enqueued
     // (under a cutoff only the tiles of the passing length window write through orig[]; the gather is a fixed 10-12 bytes per
     // candidate of the WHOLE corpus, so it pays from a window of ~30 % of the tiles on: measured break-even, bench.py --ragged --cutoff)
     const bool wide_window = (uint64_t)(p.tile_end - p.tile_begin) * 10 >= (uint64_t)corpus->n_tiles * 3;
@@ -1335,44 +1263,20 @@ rf_status run_many(const rf_comparator* c_in, const rf_corpus* corpus_in, rf_op 
         // the temporary: this stream's kept buffer (grown if this call needs f64 where u32 was kept); beyond 4 streams per corpus a
         // stream-ordered allocation for the call
         const size_t tmp_bytes = corpus->n_slots * elem;
-        tmp_lock = std::unique_lock<std::mutex>(corpus->gather_enqueue_mu);
         hipError_t ea = hipSuccess;
-        for (rf_corpus::GatherTmp& t : corpus->gather_tmp)
-            if (t.stream == st) {
-                if (t.bytes < tmp_bytes) {
-                    void* bigger = nullptr;
-                    ea = hipMalloc(&bigger, tmp_bytes);
-                    if (ea == hipSuccess) {
-                        (void)hipFree(t.ptr);  // (synchronizes with the work that used it)
-                        t.ptr = bigger;
-                        t.bytes = tmp_bytes;
-                    }
-                }
-                d_tmp = t.ptr;
-                kept_tmp = &t;
-                if (t.done && hipStreamWaitEvent(st, t.done, 0) != hipSuccess) (void)hipGetLastError();
-                break;
-            }
-        if (!d_tmp && ea == hipSuccess) {
-            if (corpus->gather_tmp.size() < 4) {
-                AccelTimer timer("gather temporary");
-                ea = hipMalloc(&d_tmp, tmp_bytes);
-                if (ea == hipSuccess) {
-                    hipEvent_t ev = nullptr;
-                    if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) (void)hipGetLastError(), ev = nullptr;
-                    corpus->gather_tmp.push_back({st, d_tmp, tmp_bytes, ev});
-                    kept_tmp = &corpus->gather_tmp.back();
-                }
-            } else {
-                ea = scratch_alloc(&d_tmp, tmp_bytes, st);
-                tmp_owned = true;
-            }
+        kept = corpus->gather_tmp.acquire(st, [&](rf_corpus::GatherTmp& t) { AccelTimer timer("gather temporary"); return t.reserve(tmp_bytes); }, &ea);
+        if (kept) {
+            ea = kept->reserve(tmp_bytes);
+            d_tmp = kept->ptr;
+        } else if (ea == hipSuccess) {
+            ea = scratch_alloc(&d_tmp, tmp_bytes, st);
+            tmp_owned = true;
         }
         if (ea != hipSuccess) {  // no room for the temporary: scattered stores through orig[] as before (not an error)
             (void)hipGetLastError();
             d_tmp = nullptr;
             tmp_owned = false;
-            tmp_lock.unlock();
+            kept.release();
         } else {
             p.out = d_tmp;
             p.orig = corpus->d_slot_ident;
@@ -1391,7 +1295,7 @@ rf_status run_many(const rf_comparator* c_in, const rf_corpus* corpus_in, rf_op 
         }
         RF_HIP(ea);
     }
-    std::unique_lock<std::mutex> filter_lock;  // held while a filter pass and the scan over its list are enqueued
+    rf_corpus::TileLease tl;  // held while a filter pass and the scan over its list are enqueued
     // (... and the small-band scans of a single-length corpus: tiles with a few lanes left are listed for a dense second pass, rf_band.hip launch_band)
     const bool band_lists = p.band && raw == RAW_LEV && corpus->uniform && !p.tiles && !want_slots && p.tile_step == 1 && !by_runs;
     // (... and of a bucketed corpus: its long length runs are walked as single-length corpora of their own, launch_band_runs.  RF_BAND_RUNS=0: one launch over the tiles)
@@ -1400,11 +1304,11 @@ rf_status run_many(const rf_comparator* c_in, const rf_corpus* corpus_in, rf_op 
                            p.tile_step == 1 && !by_runs && !by_origin && !p.topk_k && band_has_long_run(p, corpus);
     int band_runs_mode = 2;  // 2: every long run through launch_band, 1: the longest one only, 0: none (one launch over the tiles)
     if (p.heads8 || band_lists || band_runs) {  // (the head-plane scans: band prefilter or first look as a streaming pass, then the cutoff scan over its list)
-        filter_lock = std::unique_lock<std::mutex>(corpus->filter_enqueue_mu);
-        p.tile_list_buf = corpus_tile_list(corpus, st);
-        corpus_lane_buffers(corpus, &p);
-        if ((band_lists || band_runs) && p.tile_list_buf) {
-            p.band_defer_seen = p.tile_list_buf + tile_list_words(corpus->n_tiles) - 4;
+        tl = corpus->tile_list_lease(st);
+        p.tile_list_buf = tl ? tl->ptr : nullptr;
+        p.lane_list = tl ? 1u : 0u;
+        if ((band_lists || band_runs) && tl) {
+            p.band_defer_seen = tl->ptr + tl->words - 4;
             // Which form this launch takes.  Handing tiles over pays when many tiles hold a few near candidates; on a corpus with none, or with most lanes of most tiles
             // near, it buys nothing and costs the list kernels and ~3 % of the first pass' columns.  The second pass of this stream's LAST hand-over launch left what it
             // listed in pinned memory (E tiles, S lanes, of N tiles at column a); read here without waiting -- whatever launch it is from, it only steers speed:
@@ -1412,22 +1316,13 @@ rf_status run_many(const rf_comparator* c_in, const rf_corpus* corpus_in, rf_op 
             // (tiles alive at a: the listed ones, or -- when the listed ones sit right at the lane limit, so that most live tiles are above it -- all of them).
             // Below 25 % the plain kernel runs, and every 16th launch looks again.  RF_BAND_DEFER_ADAPT=0: always hand over.
             static const bool adapt = [] { const char* e = getenv("RF_BAND_DEFER_ADAPT"); return !e || atoi(e) != 0; }();
-            rf_corpus::TileList& tl = corpus->tile_lists.front();  // (corpus_tile_list moved this stream's list to the front)
-            if (!tl.band_report) {
-                void* hp = nullptr;
-                if (hipHostMalloc(&hp, 64, hipHostMallocMapped | hipHostMallocPortable) == hipSuccess) {
-                    std::memset(hp, 0, 64);
-                    tl.band_report = static_cast<volatile uint32_t*>(hp);
-                } else {
-                    (void)hipGetLastError();
-                }
-            }
-            p.band_report = const_cast<uint32_t*>(tl.band_report);
-            if (adapt && tl.band_report) {
+            volatile uint32_t* report = tl->report();
+            p.band_report = const_cast<uint32_t*>(report);
+            if (adapt && report) {
                 bool pays = false;
-                if (tl.band_report[3] != 0) {
-                    const double E = tl.band_report[0], S = tl.band_report[1], N = tl.band_report[2], a = tl.band_report[4], lanes_max = tl.band_report[5];
-                    const double L = tl.band_report[6], rest = L > a ? L - a : 0.0;  // (the length of the launch that reported: a bucketed corpus' last run)
+                if (report[3] != 0) {
+                    const double E = report[0], S = report[1], N = report[2], a = report[4], lanes_max = report[5];
+                    const double L = report[6], rest = L > a ? L - a : 0.0;  // (the length of the launch that reported: a bucketed corpus' last run)
                     const double saved = E * rest - S / 64.0 * L;
                     const bool at_the_limit = E > 0 && S / E > 0.75 * lanes_max;
                     const double plain = N * a + (at_the_limit ? N : E) * rest;
@@ -1435,7 +1330,7 @@ rf_status run_many(const rf_comparator* c_in, const rf_corpus* corpus_in, rf_op 
                 }
                 // (no report yet: the stream's FIRST launch hands over, the ones enqueued behind it before its report is in do not -- a host that enqueues ahead
                 // would otherwise send a dozen launches down a road nobody has measured)
-                const bool look = (tl.band_plain_calls++ & 15u) == 0;
+                const bool look = (tl->band_plain_calls++ & 15u) == 0;
                 if (!pays && !look) p.band_defer_seen = nullptr;  // (launch_band: the plain kernel)
                 // (a bucketed corpus pays for the hand-over with a launch sequence PER length run -- 13 runs of 770 k candidates: 626 instead of 183 us on random
                 // rows: all runs only while it pays; a look peels off the longest run alone, the rest stays one launch over the tiles)
@@ -1450,10 +1345,7 @@ rf_status run_many(const rf_comparator* c_in, const rf_corpus* corpus_in, rf_op 
                      (int)raw, p.words, p.early, p.first_check, p.band, p.heads8 != nullptr, p.head_need, p.head_k, p.tile_list_buf != nullptr, (int)by_runs, (int)by_origin,
                      d_tmp != nullptr, p.tile_begin, p.tile_end, corpus->n_tiles, p.prefill_none, p.data6 != nullptr);
     hipError_t e = by_runs ? launch_scan_runs(raw, p, c, corpus, op, f64_out, st) : (band_runs && band_runs_mode != 0 && p.band_defer_seen ? launch_band_runs(raw, p, corpus, st, band_runs_mode == 1) : launch_scan(raw, p, st, nullptr));
-    if (filter_lock.owns_lock()) {
-        if (p.tile_list_buf) corpus_tile_list_done(corpus, st);
-        filter_lock.unlock();
-    }
+    tl.release();
     if (p.long_scratch) (void)scratch_free(p.long_scratch, st);
     if (d_tmp) {
         if (e == hipSuccess)
@@ -1461,8 +1353,7 @@ rf_status run_many(const rf_comparator* c_in, const rf_corpus* corpus_in, rf_op 
                                                               (uint32_t)corpus->n, f64_out, st)
                                        : launch_gather_results(d_tmp, corpus->d_slot_of, d_out, (uint32_t)corpus->n, f64_out, st);
         if (tmp_owned) (void)scratch_free(d_tmp, st);
-        else if (kept_tmp && kept_tmp->done && hipEventRecord(kept_tmp->done, st) != hipSuccess) (void)hipGetLastError();
-        if (tmp_lock.owns_lock()) tmp_lock.unlock();
+        kept.release();
     }
     if (e == hipSuccess && out_mem == RF_MEM_HOST) {
         e = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st);

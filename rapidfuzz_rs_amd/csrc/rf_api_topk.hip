@@ -49,56 +49,22 @@ static rf_status topk_core(const rf_comparator* c_in, const rf_corpus* corpus_in
     p.heads8 = corpus->uniform ? corpus_head8_plane(corpus, p, raw, st) : nullptr;
     p.heads6 = p.heads8 ? corpus_head6_plane(corpus, st) : nullptr;
     if (corpus->uniform) plan_band_filter(c, corpus, op, false, &p, corpus->uniform_len);
-    // persistent per-(corpus, stream) scratch; capacity = every workgroup publishing a full 64-entry list.  At most kTopkStreams
-    // streams hold one: a further stream takes over the least recently used stream's scratch (after that stream's work has drained) --
-    // a process that makes a stream per request must not grow the corpus by 2 MB (+ 4 bytes per candidate for the score vector of
-    // the multi-word path) per stream it has ever used.  The lookup and the enqueue section are ONE critical section (a takeover
-    // between a thread's lookup and its launches would hand its scratch to another stream).
-    std::lock_guard<std::mutex> enqueue_lock(owner->topk_enqueue_mu);
-    constexpr size_t kTopkStreams = 8;
-    rf_corpus::TopkScratch sc;
-    {
-        std::lock_guard<std::mutex> lock(owner->scratch_mu);
-        auto& lru = owner->topk_lru;  // most recently used first
-        auto it = owner->topk_scratch.find(st);
-        if (it != owner->topk_scratch.end()) {
-            sc = it->second;
-            lru.erase(std::remove(lru.begin(), lru.end(), st), lru.end());
-        } else if (owner->topk_scratch.size() >= kTopkStreams && !lru.empty()) {
-            const hipStream_t victim = lru.back();
-            lru.pop_back();
-            sc = owner->topk_scratch[victim];  // bound and counters are left re-armed by every call
-            (void)hipEventSynchronize(sc.done);  // (the event behind its last call -- not the stream handle, whose stream may be gone)
-            owner->topk_scratch.erase(victim);
-            owner->topk_scratch.emplace(st, sc);
-        } else {
-            // [64 way segments of candidate keys | root table 64 x 64 keys | bound (u64, own line) | control block 65 x 128 B]
-            const size_t ways = 64, per_way = ((size_t)scan_grid_full(corpus->n_tiles) + ways - 1) / ways;  // (the largest grid any top-k launch uses)
-            sc.seg_cap = (uint32_t)(per_way * kWave);
-            const size_t cand_bytes = ways * sc.seg_cap * sizeof(uint64_t), root_bytes = ways * kWave * sizeof(uint64_t), ctl_bytes = 65 * 128;
-            uint8_t* mem = nullptr;
-            RF_HIP(hipMalloc((void**)&mem, cand_bytes + root_bytes + 128 + ctl_bytes));
-            sc.cand = reinterpret_cast<uint64_t*>(mem);
-            sc.root = reinterpret_cast<uint64_t*>(mem + cand_bytes);
-            sc.bound = reinterpret_cast<uint64_t*>(mem + cand_bytes + root_bytes);
-            sc.ctl = reinterpret_cast<uint32_t*>(mem + cand_bytes + root_bytes + 128);
-            hipError_t e0 = hipMemsetAsync(sc.bound, 0xFF, sizeof(uint64_t), st);
-            if (e0 == hipSuccess) e0 = hipMemsetAsync(sc.ctl, 0, ctl_bytes, st);
-            if (e0 == hipSuccess) e0 = hipEventCreateWithFlags(&sc.done, hipEventDisableTiming);
-            if (e0 != hipSuccess) {
-                (void)hipFree(mem);
-                set_error(std::string("top-k scratch: ") + hipGetErrorString(e0));
-                return RF_ERR_HIP;
-            }
-            owner->topk_scratch.emplace(st, sc);
-        }
-        lru.insert(lru.begin(), st);
+    // persistent per-(corpus, stream) scratch (rf_corpus::TopkScratch).  At most 8 streams hold one: a further stream takes over the
+    // least recently used stream's scratch (after that stream's work has drained) -- a process that makes a stream per request must not
+    // grow the corpus by 2 MB (+ 4 bytes per candidate for the score vector of the multi-word path) per stream it has ever used.  The
+    // lease is held from the lookup through the enqueue section: a takeover between a thread's lookup and its launches would hand its
+    // scratch to another stream, and host threads sharing a stream must not interleave two calls' launch sequences.
+    hipError_t ea = hipSuccess;
+    auto sc = owner->topk_scratch.acquire(st, [&](rf_corpus::TopkScratch& t) { return t.make(corpus->n_tiles, st); }, &ea);
+    if (!sc) {
+        set_error(std::string("top-k scratch: ") + hipGetErrorString(ea));
+        return ea == hipErrorOutOfMemory ? RF_ERR_OOM : RF_ERR_HIP;
     }
-    p.topk_bound = sc.bound;
-    p.topk_cand = sc.cand;
-    p.topk_seg_cap = sc.seg_cap;
-    p.topk_ctl = sc.ctl;
-    p.topk_root = sc.root;
+    p.topk_bound = sc->bound;
+    p.topk_cand = sc->cand;
+    p.topk_seg_cap = sc->seg_cap;
+    p.topk_ctl = sc->ctl;
+    p.topk_root = sc->root;
     p.topk_out = d_best;
     p.topk_k = k;
     p.topk_desc = *desc;
@@ -119,16 +85,8 @@ static rf_status topk_core(const rf_comparator* c_in, const rf_corpus* corpus_in
     if (asm_scan && (via_scores >= 2 || (via_scores == 1 && raw == RAW_LEV && p.words >= 2))) {
         uint32_t* d_scores = d_all;
         if (!d_scores) {
-            std::lock_guard<std::mutex> lock(owner->scratch_mu);
-            rf_corpus::TopkScratch& slot = owner->topk_scratch[st];
-            if (slot.scores_cap < corpus->n) {
-                if (slot.scores) (void)hipFree(slot.scores);  // (synchronizes with the work that used it)
-                slot.scores = nullptr;
-                slot.scores_cap = 0;
-                RF_HIP(hipMalloc((void**)&slot.scores, corpus->n * sizeof(uint32_t)));
-                slot.scores_cap = corpus->n;
-            }
-            d_scores = slot.scores;
+            RF_HIP(sc->scores.reserve(corpus->n * sizeof(uint32_t)));
+            d_scores = static_cast<uint32_t*>(sc->scores.ptr);
         }
         const rf_status rs = run_many(c_in, corpus_in, op, args, d_scores, RF_MEM_DEVICE, st, false);
         hipError_t e = rs == RF_OK ? launch_topk_scores(p, d_scores, (uint32_t)corpus->n, st) : hipSuccess;
@@ -136,27 +94,17 @@ static rf_status topk_core(const rf_comparator* c_in, const rf_corpus* corpus_in
         if (out_all && out_all_mem == RF_MEM_HOST) (void)scratch_free(d_all, st);
         if (rs != RF_OK) return rs;
         if (e != hipSuccess) {
-            std::lock_guard<std::mutex> lock(owner->scratch_mu);
-            (void)hipStreamSynchronize(st);
-            auto it = owner->topk_scratch.find(st);
-            if (it != owner->topk_scratch.end()) {
-                (void)hipFree(it->second.cand);
-                if (it->second.scores) (void)hipFree(it->second.scores);
-                if (it->second.done) (void)hipEventDestroy(it->second.done);
-                owner->topk_scratch.erase(it);
-                owner->topk_lru.erase(std::remove(owner->topk_lru.begin(), owner->topk_lru.end(), st), owner->topk_lru.end());
-            }
+            sc.discard();
             set_error(std::string("top-k: ") + hipGetErrorString(e));
             return RF_ERR_HIP;
         }
-        (void)hipEventRecord(sc.done, st);
         return RF_OK;
     }
-    std::unique_lock<std::mutex> filter_lock;
+    rf_corpus::TileLease list;
     if (p.heads8) {
-        filter_lock = std::unique_lock<std::mutex>(corpus->filter_enqueue_mu);
-        p.tile_list_buf = corpus_tile_list(corpus, st);
-        corpus_lane_buffers(corpus, &p);
+        list = corpus->tile_list_lease(st);
+        p.tile_list_buf = list ? list->ptr : nullptr;
+        p.lane_list = list ? 1u : 0u;
     }
     hipError_t e = hipSuccess;
     // Sample pass: the top-k of ~1000 evenly spaced tiles costs 0.1 % of the scan and its k-th best key is a valid
@@ -178,20 +126,11 @@ static rf_status topk_core(const rf_comparator* c_in, const rf_corpus* corpus_in
     if (e == hipSuccess && out_all && out_all_mem == RF_MEM_HOST) e = hipMemcpyAsync(out_all, d_all, corpus->n * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
     if (out_all && out_all_mem == RF_MEM_HOST) (void)scratch_free(d_all, st);  // (on the failure paths too: ADVICE r4)
     if (e != hipSuccess) {
-        // the scratch may be left half-armed: drop it so the next call starts from a fresh one
-        std::lock_guard<std::mutex> lock(owner->scratch_mu);
-        (void)hipStreamSynchronize(st);
-        (void)hipFree(sc.cand);
-        if (sc.scores) (void)hipFree(sc.scores);
-        if (sc.done) (void)hipEventDestroy(sc.done);
-        owner->topk_scratch.erase(st);
-        owner->topk_lru.erase(std::remove(owner->topk_lru.begin(), owner->topk_lru.end(), st), owner->topk_lru.end());
+        sc.discard();  // (the scratch may be left half-armed)
         set_error(std::string("top-k: ") + hipGetErrorString(e));
         return RF_ERR_HIP;
     }
-    (void)hipEventRecord(sc.done, st);  // what a later take-over of this scratch / tile list waits for
-    if (p.tile_list_buf) corpus_tile_list_done(corpus, st);
-    return RF_OK;
+    return RF_OK;  // (the leases record what a later take-over of this scratch / tile list waits for)
 }
 
 // ---- the general top-k path: scan to a score vector, then exact selection over it (rf_select.hip) ------------------

@@ -12,6 +12,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <deque>
+#include <list>
 #include <cstdio>
 #include <atomic>
 #include <unordered_map>
@@ -24,6 +25,7 @@
 #include <mutex>
 #include <new>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "rf_internal.hpp"
@@ -53,6 +55,134 @@ struct DeviceGuard {
     {
         if (prev >= 0) (void)hipSetDevice(prev);
     }
+};
+
+// What a corpus keeps per stream that scans it (rf_corpus: top-k scratch, gather temporaries, tile lists): at most `cap` entries
+// {stream, done event, T}, most recently used first.  acquire() returns a Lease that holds the cache's mutex until it is released
+// or destroyed (host threads sharing a stream must not interleave their uses of one buffer), with
+//   - the stream's own entry, after a hipStreamWaitEvent on its `done` (a new stream may have been handed a destroyed stream's
+//     handle value while that stream's work is in flight: ADVICE r4), else
+//   - a new entry filled by the caller's make(T&) while there is room (a failure drops it, *err says why), else
+//   - take_over: the least recently used entry once its `done` has completed (the event, never the old stream handle: that
+//     stream may be gone); otherwise no entry, and the caller allocates for the call.
+// Releasing the lease records `done` behind what was enqueued under it -- on every exit, error returns included.  T is
+// default-constructible, frees its buffers in its destructor and reports their bytes().
+// Lock order where one call holds several leases: top-k -> gather -> tile list (the via-scores top-k runs run_many under its lease).
+struct NoCopy {
+    NoCopy() = default;
+    NoCopy(const NoCopy&) = delete;
+    NoCopy& operator=(const NoCopy&) = delete;
+};
+template <class T>
+class StreamCache {
+    struct Entry : NoCopy {
+        hipStream_t stream;
+        hipEvent_t done;
+        T value;
+        Entry(hipStream_t s, hipEvent_t d) : stream(s), done(d) {}
+        ~Entry() { (void)hipEventDestroy(done); }
+    };
+    mutable std::mutex mu_;
+    std::list<Entry> entries_;  // (stable addresses)
+    const size_t cap_;
+    const bool take_over_;
+
+public:
+    StreamCache(size_t cap, bool take_over) : cap_(cap), take_over_(take_over) {}
+    class Lease {
+        friend class StreamCache;
+        std::unique_lock<std::mutex> lock_;
+        std::list<Entry>* entries_ = nullptr;
+        Entry* e_ = nullptr;  // nullptr: no entry (the lock may still be held)
+
+    public:
+        Lease() = default;
+        Lease(Lease&& o) noexcept : lock_(std::move(o.lock_)), entries_(o.entries_), e_(std::exchange(o.e_, nullptr)) {}
+        Lease& operator=(Lease&& o) noexcept
+        {
+            release();
+            lock_ = std::move(o.lock_), entries_ = o.entries_, e_ = std::exchange(o.e_, nullptr);
+            return *this;
+        }
+        ~Lease() { release(); }
+        explicit operator bool() const { return e_ != nullptr; }
+        T* operator->() const { return &e_->value; }
+        void release()  // everything that uses the entry has been enqueued
+        {
+            if (e_ && hipEventRecord(e_->done, e_->stream) != hipSuccess) (void)hipGetLastError();
+            e_ = nullptr;
+            if (lock_.owns_lock()) lock_.unlock();
+        }
+        void discard()  // the entry may be left half-armed: free it once its stream's work is done (the next call starts from a fresh one)
+        {
+            if (e_) {
+                (void)hipStreamSynchronize(e_->stream);
+                entries_->pop_front();  // (the leased entry: acquire() put it in front, and the lock has been held since)
+                e_ = nullptr;
+            }
+            release();
+        }
+    };
+    template <class Make>
+    Lease acquire(hipStream_t st, Make&& make, hipError_t* err = nullptr)
+    {
+        Lease l;
+        l.lock_ = std::unique_lock<std::mutex>(mu_);
+        l.entries_ = &entries_;
+        if (err) *err = hipSuccess;
+        for (auto it = entries_.begin(); it != entries_.end(); ++it)
+            if (it->stream == st) {
+                entries_.splice(entries_.begin(), entries_, it);
+                if (hipStreamWaitEvent(st, it->done, 0) != hipSuccess) (void)hipGetLastError();
+                l.e_ = &*it;
+                return l;
+            }
+        if (entries_.size() < cap_) {
+            hipEvent_t done = nullptr;
+            hipError_t e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
+            if (e == hipSuccess) {
+                entries_.emplace_front(st, done);
+                e = make(entries_.front().value);
+                if (e == hipSuccess) l.e_ = &entries_.front();
+                else entries_.pop_front();
+            }
+            if (e != hipSuccess) (void)hipGetLastError();
+            if (err) *err = e;
+        } else if (take_over_) {
+            entries_.splice(entries_.begin(), entries_, std::prev(entries_.end()));
+            (void)hipEventSynchronize(entries_.front().done);
+            entries_.front().stream = st;
+            l.e_ = &entries_.front();
+        }
+        return l;
+    }
+    uint64_t bytes() const
+    {
+        std::lock_guard<std::mutex> lock(mu_);
+        uint64_t b = 0;
+        for (const Entry& e : entries_) b += e.value.bytes();
+        return b;
+    }
+};
+// a device buffer that grows in place (hipFree synchronizes with the work that used the smaller one)
+struct DeviceBuf : NoCopy {
+    void* ptr = nullptr;
+    size_t cap = 0;  // bytes
+    ~DeviceBuf()
+    {
+        if (ptr) (void)hipFree(ptr);
+    }
+    hipError_t reserve(size_t bytes)
+    {
+        if (cap >= bytes) return hipSuccess;
+        void* bigger = nullptr;
+        const hipError_t e = hipMalloc(&bigger, bytes);
+        if (e != hipSuccess) return e;
+        if (ptr) (void)hipFree(ptr);
+        ptr = bigger, cap = bytes;
+        return hipSuccess;
+    }
+    uint64_t bytes() const { return cap; }
 };
 
 }  // namespace rf
@@ -118,52 +248,87 @@ struct rf_corpus {
     uint8_t sigma[256];           // symbol renaming: the packed corpus stores sigma[c] for candidate byte c
     float sym_freq[256] = {0};    // relative frequency of candidate byte c (from the histogram sigma is made of; all zero = unknown)
     uint8_t* d_sigma = nullptr;   // device copy
-    // top-k scratch, one per stream the corpus has been searched on: [candidate keys by way | root table | bound | counters].  The
-    // kernels leave bound/counters re-armed, so a top-k call is two launches (one under a tight cutoff) and no
-    // allocation or memset (topk_core()).
-    struct TopkScratch {
-        uint64_t* cand = nullptr;  // (also the base of the allocation)
-        uint64_t* root = nullptr;
-        uint64_t* bound = nullptr;
+    mutable std::mutex scratch_mu;  // guards the structures a call builds on first use (the mutable members here, the caches below aside)
+    // Per-stream buffers (StreamCache), at most 8 top-k scratches, 4 gather temporaries and 4 tile lists.  The top-k scratch: [64 way
+    // segments of candidate keys | root table 64 x 64 keys | bound (u64, own line) | control block 65 x 128 B], room for every workgroup
+    // of the largest grid any top-k launch uses to publish a full 64-entry list.  The kernels leave bound / counters re-armed, so a
+    // top-k call is two launches (one under a tight cutoff) that hand state to each other through it and no allocation or memset
+    // (topk_core()); + the score vector of the scan + one-pass top-k (rf_api_topk.hip).
+    struct TopkScratch : NoCopy {
+        uint64_t *cand = nullptr, *root = nullptr, *bound = nullptr;  // (cand: the base of the allocation)
         uint32_t* ctl = nullptr;
         uint32_t seg_cap = 0;
-        hipEvent_t done = nullptr;   // recorded behind the last call's launches on this scratch (what a take-over waits for)
-        uint32_t* scores = nullptr;  // score vector of the scan + one-pass top-k (rf_api_topk.hip), kept like the rest; own allocation
-        size_t scores_cap = 0;       // in candidates
+        size_t alloc = 0;  // bytes at cand
+        DeviceBuf scores;
+        ~TopkScratch()
+        {
+            if (cand) (void)hipFree(cand);
+        }
+        hipError_t make(uint32_t n_tiles, hipStream_t st)
+        {
+            const size_t ways = 64, per_way = ((size_t)scan_grid_full(n_tiles) + ways - 1) / ways;
+            seg_cap = (uint32_t)(per_way * kWave);
+            const size_t cand_bytes = ways * seg_cap * sizeof(uint64_t), root_bytes = ways * kWave * sizeof(uint64_t), ctl_bytes = 65 * 128;
+            hipError_t e = hipMalloc((void**)&cand, cand_bytes + root_bytes + 128 + ctl_bytes);
+            if (e != hipSuccess) return e;
+            alloc = cand_bytes + root_bytes + 128 + ctl_bytes;
+            uint8_t* mem = reinterpret_cast<uint8_t*>(cand);
+            root = reinterpret_cast<uint64_t*>(mem + cand_bytes);
+            bound = reinterpret_cast<uint64_t*>(mem + cand_bytes + root_bytes);
+            ctl = reinterpret_cast<uint32_t*>(mem + cand_bytes + root_bytes + 128);
+            e = hipMemsetAsync(bound, 0xFF, sizeof(uint64_t), st);
+            return e == hipSuccess ? hipMemsetAsync(ctl, 0, ctl_bytes, st) : e;
+        }
+        uint64_t bytes() const { return alloc + scores.bytes(); }
     };
-    mutable std::mutex scratch_mu;
-    mutable std::map<hipStream_t, TopkScratch> topk_scratch;
-    mutable std::vector<hipStream_t> topk_lru;  // the streams of topk_scratch, most recently used first (rf_api_topk.hip: at most 8 hold a scratch)
-    // A top-k call is two launches that hand state to each other through the scratch (sample scan -> bound -> scan, each
-    // selecting in its last workgroup and re-arming it).  Host threads sharing a stream must not interleave those sequences: the enqueue
-    // section of topk_core() runs under this lock (kernels of one stream then execute in enqueue order).
-    mutable std::mutex topk_enqueue_mu;
-    // The gather path's slot-ordered temporary (run_many), one per stream the corpus has been scanned on that way, kept for the
-    // corpus' lifetime: a stream-ordered hipMallocAsync / hipFreeAsync pair per call made the SUBMISSION of such a step wait for the
-    // previous step (measured: 560 us per call to submit a 575 us step; 11 us with the buffer kept).  A call's scan + gather are
-    // enqueued under gather_enqueue_mu: host threads sharing a stream must not interleave two uses of the same buffer.
-    struct GatherTmp {
-        hipStream_t stream;
-        void* ptr;
-        size_t bytes;
-        hipEvent_t done;  // recorded behind the gather that last read the buffer; the next use makes its stream wait for it (free on the stream the
-                          // buffer was used on, and what orders a NEW stream that was handed a destroyed stream's handle value: ADVICE r4)
-    };
-    mutable std::vector<GatherTmp> gather_tmp;
-    mutable std::mutex gather_enqueue_mu;
-    // head_filter_kernel's tile lists (rf_scan.hip), one per stream such a cutoff scan has run on: 8 bytes per tile.  The filter
-    // pass and the scan that walks its list are enqueued under filter_enqueue_mu (host threads sharing a stream).
-    struct TileList {
-        hipStream_t stream;
-        uint32_t* ptr;
-        hipEvent_t done;  // recorded behind the last scan that walked the list (corpus_tile_list_done): a take-over waits for THIS, never
-                          // for the stream handle -- its owner may have destroyed the stream long ago, and the runtime crashes on a dead handle
-        volatile uint32_t* band_report = nullptr;  // pinned, 64 bytes: what this stream's last hand-over launch of the small-band scan listed (rf_band.hip band_sparse_kernel
-                                                   // writes it; run_many reads it, without waiting, to choose the next launch's form); nullptr = no pinned memory
+    // The gather path's slot-ordered temporary (run_many), grown when a call needs f64 where u32 was kept: a stream-ordered
+    // hipMallocAsync / hipFreeAsync pair per call made the SUBMISSION of such a step wait for the previous step (measured: 560 us per
+    // call to submit a 575 us step; 11 us with the buffer kept).
+    using GatherTmp = DeviceBuf;
+    // head_filter_kernel's tile list (rf_scan.hip), the lane lists and the small-band hand-over's (rf_band.hip).  Words: round 5's
+    // layout (packed count, <= 16 K per-wavefront counts and offsets, their segments -- n_tiles + 2 per wavefront of rounding --, the
+    // packed list) needs 2 n_tiles + 5 x 16384; the lane lists (lane_list_pack_kernel: 16-byte entries in the segments and in the
+    // packed list) four times the entries, + one word per dense tile (its first[]); the last 4 words: launch_band's count of
+    // hand-over candidates, zero between launches.
+    struct TileList : NoCopy {
+        uint32_t* ptr = nullptr;
+        size_t words = 0;
+        volatile uint32_t* band_report = nullptr;  // pinned, 64 bytes: what this stream's last hand-over launch of the small-band scan listed (rf_band.hip
+                                                   // band_sparse_kernel writes it; run_many reads it, without waiting, to choose the next launch's form)
         uint32_t band_plain_calls = 0;             // launches since that choice last fell on the plain kernel
+        ~TileList()
+        {
+            if (ptr) (void)hipFree(ptr);
+            if (band_report) (void)hipHostFree(const_cast<uint32_t*>(band_report));
+        }
+        hipError_t make(uint32_t n_tiles, hipStream_t st)
+        {
+            const size_t w = 9 * (size_t)n_tiles + 12 * 16384 + 64;
+            const hipError_t e = hipMalloc((void**)&ptr, w * sizeof(uint32_t));
+            if (e != hipSuccess) return e;
+            words = w;
+            if (hipMemsetAsync(ptr + words - 4, 0, 4 * sizeof(uint32_t), st) != hipSuccess) (void)hipGetLastError();
+            return hipSuccess;
+        }
+        volatile uint32_t* report()  // band_report, allocated on first use; nullptr = no pinned memory to be had
+        {
+            if (!band_report) {
+                void* hp = nullptr;
+                if (hipHostMalloc(&hp, 64, hipHostMallocMapped | hipHostMallocPortable) == hipSuccess) band_report = static_cast<volatile uint32_t*>(std::memset(hp, 0, 64));
+                else (void)hipGetLastError();
+            }
+            return band_report;
+        }
+        uint64_t bytes() const { return (uint64_t)words * sizeof(uint32_t); }
     };
-    mutable std::vector<TileList> tile_lists;
-    mutable std::mutex filter_enqueue_mu;
+    mutable StreamCache<TopkScratch> topk_scratch{8, true};  // (on `parent` for a translated image)
+    mutable StreamCache<GatherTmp> gather_tmp{4, false};     // (a fifth stream: a stream-ordered allocation for the call)
+    mutable StreamCache<TileList> tile_lists{4, true};       // (a fifth stream takes a list over rather than the scan silently falling back to the slower in-kernel filter: VERDICT r3 weak #6)
+    using TileLease = StreamCache<TileList>::Lease;
+    TileLease tile_list_lease(hipStream_t st) const  // no entry in the lease: no list to be had, the scan then filters inside the cutoff kernel
+    {
+        return tile_lists.acquire(st, [&](TileList& t) { return t.make(n_tiles, st); });
+    }
     mutable std::atomic<uint32_t> filter_last_survivors{0};  // rf_filter_*: how many candidates the last lane-compacted call's first pass left (few: one workgroup finishes the call)
     mutable std::atomic<uint32_t> hint_trust{0};  // score_hint scans (run_many_hinted): consecutive hinted calls whose first pass resolved >= 70 % of this corpus -- while it counts, the sample (a launch and a host synchronization) is taken on every 16th call only
     // u32 ("char") corpora: the stored byte is the symbol's id in THIS corpus' alphabet.  Ids 0..253 are the 254 most
@@ -269,8 +434,5 @@ RF_LOCAL const uint32_t* corpus_head6_plane(const rf_corpus* corpus, hipStream_t
 RF_LOCAL const uint32_t* corpus_data6(const rf_corpus* corpus, hipStream_t st);                                        // rf_api_scan.hip
 RF_LOCAL const uint8_t* corpus_head8_plane(const rf_corpus* corpus, const ScanParams& p, RawKind raw, hipStream_t st);    // rf_api_scan.hip
 RF_LOCAL void plan_band_filter(const rf_comparator* c, const rf_corpus* corpus, rf_op op, bool f64_out, ScanParams* p, uint32_t len2);  // rf_api_scan.hip
-RF_LOCAL void corpus_tile_list_done(const rf_corpus* corpus, hipStream_t st);                                           // rf_api_scan.hip
-RF_LOCAL uint32_t* corpus_tile_list(const rf_corpus* corpus, hipStream_t st);                                             // rf_api_scan.hip
-RF_LOCAL void corpus_lane_buffers(const rf_corpus* corpus, ScanParams* p);                                                // rf_api_scan.hip
 RF_LOCAL rf_status run_many(const rf_comparator* c_in, const rf_corpus* corpus_in, rf_op op, const rf_args* args, void* out, rf_mem out_mem, void* stream, bool f64_out);  // rf_api_scan.hip
 }  // extern "C"

@@ -3048,7 +3048,8 @@ assert (ra == rb).all() and int((ra != 0xFFFFFFFF).sum()) >= 1
 
 def test_five_streams_share_the_tile_lists_of_one_corpus():
     """the head-plane scans keep one tile list per stream, at most 4 per corpus; a fifth stream used to fall back
-    silently to the in-kernel filter.  Now the least recently used list changes hands: six streams in turn, twice, same values."""
+    silently to the in-kernel filter.  Now the least recently used list changes hands: six streams in turn, twice, same values, and
+    the corpus' device footprint stops growing after four streams."""
     import torch
 
     host = synth.rows_host((1 << 20) + 3, 64, seed=15)
@@ -3060,12 +3061,53 @@ def test_five_streams_share_the_tile_lists_of_one_corpus():
     exp = _expect_u32(o.levenshtein.BatchComparator(q).rows(N.OP_DISTANCE, host, nthreads=8, score_cutoff=3))
     streams = [torch.cuda.Stream() for _ in range(6)]
     outs = [torch.empty(len(host), dtype=torch.int32, device="cuda") for _ in streams]
+    sizes = []
     for _ in range(2):
         for st, out in zip(streams, outs):
             bc.distance_many(corpus, out=out, stream=st.cuda_stream, score_cutoff=3)
+            sizes.append(corpus.device_bytes)
     torch.cuda.synchronize()
     for out in outs:
         assert (out.cpu().numpy().view(np.uint32) == exp).all()
+    assert sizes[0] < sizes[1] < sizes[2] < sizes[3] and all(s == sizes[3] for s in sizes[3:]), sizes
+
+
+def test_six_streams_share_the_gather_temporaries_of_one_corpus():
+    """The slot-ordered temporary of a large bucketed corpus' scan (then one gather into original order) is kept per stream, at most 4
+    per corpus, grown in place when an f64 call follows a u32 one; a fifth and a sixth stream take a per-call allocation.  Six streams in
+    turn, twice, u32 distance then f64 normalized_distance on each: the oracle's values, every call on the gather path (RF_TRACE_PLAN is
+    read once per process: a child process), and the corpus' device footprint stops growing after four streams."""
+    import subprocess
+    import sys
+
+    code = r"""
+import sys, numpy as np, torch
+sys.path.insert(0, %r)
+import rapidfuzz_rs_amd as rf
+from rapidfuzz_rs_amd import _native as N
+from rapidfuzz_rs_amd.utils import synth
+from oracle import oracle as o
+data, offsets = synth.ragged_host((1 << 20) + 5, 64, seed=17, min_len=1)
+q = synth.query(32, 18)
+corpus = rf.Corpus.from_ragged(data, offsets)
+bc, ob = rf.distance.levenshtein.BatchComparator(q), o.levenshtein.BatchComparator(q)
+ed = ob.many(N.OP_DISTANCE, data, offsets, nthreads=8)
+ed = np.where(ed == np.uint64(2**64 - 1), np.uint32(0xFFFFFFFF), ed.astype(np.uint32))
+en = ob.many(N.OP_NORMALIZED_DISTANCE, data, offsets, nthreads=8)
+streams = [torch.cuda.Stream() for _ in range(6)]
+sizes = []
+for _ in range(2):
+    for st in streams:
+        assert (bc.distance_many(corpus, stream=st.cuda_stream) == ed).all()
+        got = bc.normalized_distance_many(corpus, stream=st.cuda_stream)
+        assert ((got == en) | (np.isnan(got) & np.isnan(en))).all()
+        sizes.append(corpus.device_bytes)
+assert sizes[0] < sizes[1] < sizes[2] < sizes[3] and all(s == sizes[3] for s in sizes[3:]), sizes
+""" % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=dict(os.environ, RF_TRACE_PLAN="1"))
+    assert r.returncode == 0, r.stderr[-3000:]
+    plans = [ln for ln in r.stderr.splitlines() if ln.startswith("[rf plan] raw=")]
+    assert len(plans) == 24 and all("gather=1" in ln for ln in plans), plans[:4]
 
 
 def test_mid_size_corpora_on_the_tiles_per_wavefront_grid():
