@@ -10,7 +10,10 @@ collective, and each step ends with the top-k all-gather the north star names (k
 `--config c5` is BASELINE.json configs[4]: ONE logical corpus of 1 B len-64 candidates split over the ranks (strong
 scaling), score_cutoff = 3, top-16 only, the RCCL all-gather + merge every step.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline` objects.
+Prints ONE JSON line on rank 0 with a `roofline` object.  A plain run does only what that line's headline needs: set-up,
+warm-up, the timed steps, --dump-outputs, the line.  `--full` adds everything else the benchmark measures or checks, after the
+timed steps: the CPU baseline and the oracle parity legs, the exchange self-check, the in-run VALU-issue ceiling and clock
+sampling, the rocprofv3 traffic passes and the `extra_configs` legs of the other BASELINE.json configs.
 """
 from __future__ import annotations
 
@@ -75,15 +78,18 @@ def parse():
     ap.add_argument("--min-len", type=int, default=1, help="--ragged: shortest candidate length (lengths uniform in [--min-len, --cand-len])")
     ap.add_argument("--slot-order", action="store_true",
                     help="--ragged: results in the corpus' SLOT order (RF_FLAG_SLOT_ORDER: no gather pass; rf_corpus_slot_index maps them back -- the parity leg does)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check what the headline does not need: CPU baseline + oracle parity (unless "
+                         "--no-cpu-baseline), exchange self-check, VALU-issue ceiling and clocks, --traffic auto and --extras auto")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: no CPU baseline and no oracle parity legs")
     ap.add_argument("--extras", default="auto", choices=["auto", "on", "off"],
-                    help="after the headline's timed region, run one short leg (own process, --extra-steps steps, own roofline + oracle parity) for "
-                         "each OTHER BASELINE.json config and report them as `extra_configs`.  auto = on for the default workload at N = 1")
+                    help="after the headline's timed region, run one short leg (own process, --extra-steps steps, --full: own roofline, CPU baseline and oracle parity) for "
+                         "each OTHER BASELINE.json config and report them as `extra_configs`.  auto = on under --full for the default workload at N = 1")
     ap.add_argument("--extra-steps", type=int, default=20, help="timed steps of each extra_configs leg (the launch-bound configs[0] leg runs 25 x as many)")
     ap.add_argument("--traffic", default="auto", choices=["auto", "on", "off"],
                     help="on: roofline.traffic from two short rocprofv3 --pmc passes of this command run after the timed region (when rocprofv3 is on the "
-                         "box; N = 1), else the committed counters of profiles/traffic.json marked as such; off: only the committed file; auto: on for "
-                         "workloads of >= 10 M candidates outside the extra legs")
+                         "box; N = 1), else the committed counters of profiles/traffic.json marked as such; off: only the committed file; auto: on under "
+                         "--full for workloads of >= 10 M candidates outside the extra legs")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU time of the baseline sample")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the last timed step returned (rank 0's view) as DIR/<name>.npy in float64: every value, or a "
@@ -274,6 +280,7 @@ def main():
                 planted[hit, pos[hit]] = sub[hit]
             rows[sel_rows] = planted
         del pidx
+    cpu_leg = args.full and not args.no_cpu_baseline  # the CPU baseline and the oracle parity legs: host copies of the corpus taken here
     sample_rows = min(n, 32_000_000)
     host_sample = None
     host_strided = None
@@ -305,7 +312,7 @@ def main():
         in_window = float(((lens - args.query_len).abs() <= (args.cutoff if args.cutoff is not None else 1 << 30)).float().mean().item())
         h_data, h_off = flat.cpu().numpy(), offsets.cpu().numpy().astype(np.uint64)
         del flat, offsets, lens
-        if rank == 0 and not args.no_cpu_baseline:
+        if rank == 0 and cpu_leg:
             m = min(n, 8_000_000)
             ragged_sample = (h_data[: int(h_off[m])], h_off[: m + 1].copy())
             pick = np.arange(0, n, 1009)
@@ -320,7 +327,7 @@ def main():
         pack_payload = int(h_off[-1])
         del h_data, h_off
     else:
-        if rank == 0 and not args.no_cpu_baseline and world == 1:  # the CPU baseline and the oracle parity leg run at N = 1 only
+        if rank == 0 and cpu_leg and world == 1:  # the CPU baseline and the oracle parity leg run at N = 1 only
             host_sample = rows[:sample_rows].cpu().numpy()
             host_strided = rows[::1009].cpu().numpy()  # every 1009-th candidate of the WHOLE shard
         t_pack = time.time()
@@ -612,8 +619,11 @@ def main():
                           "what": "the scan streams the 6-bit copy of the payload (12 bytes per started 16 symbols)"}} if moved_bpp is not None else {}),
         },
     }
-    if (args.metric in ("levenshtein", "indel", "lcs_seq", "osa") and args.query_len <= (512 if args.metric == "levenshtein" else 64) and not weights and not early
-            and os.environ.get("RF_BENCH_IN_PMC") != "1"):  # (not inside this command's own counter passes: traffic_in_run)
+    issue_probe = (args.metric in ("levenshtein", "indel", "lcs_seq", "osa") and args.query_len <= (512 if args.metric == "levenshtein" else 64) and not weights
+                   and not early and os.environ.get("RF_BENCH_IN_PMC") != "1")  # (not inside this command's own counter passes: traffic_in_run)
+    if issue_probe and not args.full:
+        result["roofline"]["bound_note"] = "VALU-issue ceiling not measured in a plain run: bench.py --full measures it and labels the bound by it"
+    if issue_probe and args.full:
         # The bit-parallel scans of this family are bound by VALU issue before they are bound by HBM.  The
         # ceiling is MEASURED here, in this process: the library's own recurrence column on register-resident pattern
         # words, no HBM / LDS / tile loop (rf_probe_issue_rate, rapidfuzz_rs_amd/csrc/rf_probe.hip).
@@ -731,7 +741,7 @@ def main():
 
         # the same for every world size when the corpus is ONE logical corpus (c5): the scaling runs must agree on it
         result["config"]["topk_checksum"] = zlib.crc32(np.array(sorted(keys), dtype=np.uint64).tobytes())
-        if args.mode == "many" and not is_f64:
+        if args.full and args.mode == "many" and not is_f64:
             # oracle-free consistency of the exchange at any world size: rank 0 ranks its OWN shard from the per-candidate
             # distances the same pass wrote (torch on the device) -- each of its k best must be in the merged list or lose to
             # the merged list's worst entry, and every merged entry that points into this shard must carry that candidate's distance
@@ -743,7 +753,7 @@ def main():
             bad = sum(1 for x in local_best if x not in keys and x < worst)
             bad += sum(1 for x in keys if index_base <= (x & 0xFFFFFFFF) < index_base + n and x not in local_best)
             result["config"]["exchange_selfcheck"] = {"rank0_shard_entries_checked": len(local_best), "inconsistent": bad}
-        if c5 and not args.no_cpu_baseline:  # (cheap: the oracle on ~1000 rows; kept at every world size -- it is the check that the shards add up)
+        if c5 and cpu_leg:  # (cheap: the oracle on ~1000 rows; kept at every world size -- it is the check that the shards add up)
             # parity of the merged top-k: the only candidates within the cutoff are planted near-duplicates (a random
             # len-64 alphanumeric string is ~55 edits from the query), and a planted row depends only on its global
             # index, so rank 0 re-creates ALL of them on the host and lets the oracle rank them
@@ -855,7 +865,7 @@ def main():
     is_headline = (args.config in (None, "c2") and args.metric == "levenshtein" and n == 100_000_000 and args.cand_len == 64 and args.query_len == 64
                    and args.cutoff is None and not weights and not args.ragged and args.mode == "many" and nq == 1 and world == 1 and not force_dist
                    and args.head_share == 0 and args.zipf == 0)
-    if args.extras == "on" or (args.extras == "auto" and is_headline):
+    if args.extras == "on" or (args.extras == "auto" and args.full and is_headline):
         # the headline's numbers are final at this point; give the GPU memory back before the legs start their own processes
         del corpus, out
         torch.cuda.empty_cache()
@@ -899,7 +909,7 @@ def extra_configs(args):
             else:
                 flags += ["--candidates", str(max(100_000, int(100_000_000 * scale)))]
         steps = args.extra_steps * (25 if name.startswith("c1_") else 1)  # (7 us steps: a handful of them measures the clock ramp, not the call)
-        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(steps), "--warmup", "5", "--extras", "off", "--traffic", "off",
+        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(steps), "--warmup", "5", "--full", "--extras", "off", "--traffic", "off",
                "--cpu-seconds", "2", "--settle-ms", "100", *flags]
         env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
         env["MASTER_PORT"] = "29577"
@@ -996,14 +1006,14 @@ def traffic_in_run(args, kernel_ms):
 
 
 def measured_traffic(args, n, kernel_ms):
-    """HBM bytes per launch: measured in this run when rocprofv3 is on the box (traffic_in_run), else from the committed rocprofv3 PMC
+    """HBM bytes per launch: measured in this run (--full, or --traffic on) when rocprofv3 is on the box (traffic_in_run), else from the committed rocprofv3 PMC
     passes of this exact workload, marked "source": "committed ..."
     (profiles/traffic.json, written by tools/rocpd_summary.py from separate --pmc FETCH_SIZE / WRITE_SIZE runs with the
     gfx950 2x FETCH_SIZE correction of MI355X_MICROARCH.md).  None when no profile matches the workload -- or when the
     kernel has changed since the counters were collected (its steady-state time then differs from this run's by more
     than 15 %): a stale counter is not evidence."""
     mode = getattr(args, "traffic", "auto")
-    if mode == "on" or (mode == "auto" and n >= 10_000_000 and getattr(args, "config", None) != "c5"):
+    if mode == "on" or (mode == "auto" and getattr(args, "full", False) and n >= 10_000_000 and getattr(args, "config", None) != "c5"):
         try:
             live = traffic_in_run(args, kernel_ms)
         except Exception:  # a measurement aid: never fails the bench line

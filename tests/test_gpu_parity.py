@@ -1597,13 +1597,14 @@ def test_rf_one_is_the_per_candidate_method():
 
 
 def test_bench_contract_small():
-    """bench.py's contract on a small corpus: ONE JSON line, last on stdout, with the required keys, a roofline, a
-    cpu_baseline and a clean parity leg; and the sharded path (top-k + all-gather + merge) at world size 1."""
+    """bench.py's contract on a small corpus: ONE JSON line, last on stdout, with the required keys, a roofline, and under
+    --full a cpu_baseline and a clean parity leg; the sharded path (top-k + all-gather + merge) at world size 1; and a plain
+    run (no --full) that prints the same headline keys and runs nothing the headline does not need."""
     import subprocess
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    base = [sys.executable, os.path.join(root, "bench.py"), "--candidates", "300000", "--steps", "3", "--warmup", "1", "--cpu-seconds", "0.5"]
+    base = [sys.executable, os.path.join(root, "bench.py"), "--candidates", "300000", "--steps", "3", "--warmup", "1", "--cpu-seconds", "0.5", "--full"]
     r = subprocess.run(base, capture_output=True, text=True, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads(r.stdout.strip().splitlines()[-1])
@@ -1619,6 +1620,13 @@ def test_bench_contract_small():
     d = json.loads(r.stdout.strip().splitlines()[-1])
     assert d["config"]["topk_found"] == 16 and d["value"] > 0
     assert d["config"]["exchange_selfcheck"]["inconsistent"] == 0 and d["config"]["exchange_selfcheck"]["rank0_shard_entries_checked"] == 16
+    r = subprocess.run([a for a in base if a != "--full"], capture_output=True, text=True, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads(r.stdout.strip().splitlines()[-1])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config", "roofline"):
+        assert key in d, key
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["unit"] == "Gpairs/s" and d["higher_is_better"] is True
+    assert not {"cpu_baseline", "parity", "extra_configs"} & set(d) and "issue_bound" not in d["roofline"], sorted(d)
 
 
 def test_bench_extra_configs_legs():
@@ -1692,7 +1700,7 @@ def test_bench_gpus_flag_spawns_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["RF_BENCH_BACKEND"] = "gloo"
     d = _bench_json([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--candidates", "200000", "--steps", "3", "--warmup", "1",
-                     "--no-cpu-baseline"], env)
+                     "--full", "--no-cpu-baseline"], env)
     assert d["n_gpus"] == 2 and d["config"]["ranks_joined"] == 2 and d["config"]["topk_found"] == 16
     assert d["config"]["exchange_selfcheck"]["inconsistent"] == 0
     # and a launcher that starts a different number of ranks than --gpus says is refused, not mis-reported
@@ -1713,7 +1721,7 @@ def test_bench_c5_preset_same_answer_for_every_world_size():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     base = [sys.executable, os.path.join(root, "bench.py"), "--config", "c5", "--total-candidates", "3000000", "--plant-every", "50000", "--steps", "3",
-            "--warmup", "1", "--cpu-seconds", "0.3"]
+            "--warmup", "1", "--cpu-seconds", "0.3", "--full"]
     d1 = _bench_json(base, env)
     assert d1["n_gpus"] == 1 and d1["scaling"] == "strong" and d1["config"]["rccl_ranks"] == 1
     assert d1["parity"]["mismatches"] == 0 and d1["parity"]["checked"] == 60 and "cpu_baseline" in d1
@@ -2860,7 +2868,7 @@ def test_full_size_c5_one_billion_candidates_through_the_rccl_path():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["MASTER_PORT"] = "29653"
-    d = _bench_json([sys.executable, os.path.join(root, "bench.py"), "--config", "c5", "--steps", "3", "--warmup", "1", "--cpu-seconds", "0.5"], env)
+    d = _bench_json([sys.executable, os.path.join(root, "bench.py"), "--config", "c5", "--steps", "3", "--warmup", "1", "--cpu-seconds", "0.5", "--full"], env)
     total_n, every, k = 1_000_000_000, 1_000_000, 16
     assert d["n_gpus"] == 1 and d["scaling"] == "strong" and d["config"]["rccl_ranks"] == 1 and d["config"]["candidates_per_gpu"] == total_n
     assert "configs[4]" in d["config"]["workload"]
@@ -2922,10 +2930,10 @@ def test_real_ranks_over_rccl_when_the_box_has_two_gpus():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "RF_BENCH_BACKEND")}
     b = _bench_json([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(world), "--candidates", "2000000", "--steps", "3", "--warmup", "1",
-                     "--no-cpu-baseline"], dict(env, RF_BENCH_FORCE_DIST="1") if world == 1 else env)
+                     "--full", "--no-cpu-baseline"], dict(env, RF_BENCH_FORCE_DIST="1") if world == 1 else env)
     assert b["n_gpus"] == world and b["config"]["rccl_ranks"] == world and b["config"]["exchange_selfcheck"]["inconsistent"] == 0
     base = [sys.executable, os.path.join(root, "bench.py"), "--config", "c5", "--total-candidates", "6000000", "--plant-every", "50000", "--steps", "3",
-            "--warmup", "1", "--cpu-seconds", "0.3"]
+            "--warmup", "1", "--cpu-seconds", "0.3", "--full"]
     d1 = _bench_json(base, env)
     assert d1["config"]["rccl_ranks"] == 1 and d1["parity"]["mismatches"] == 0
     d2 = _bench_json(base + (["--gpus", str(world)] if world > 1 else ["--shard", "dealt"]), env)

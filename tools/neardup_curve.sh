@@ -11,7 +11,7 @@ N=${2:-10000000}
 line() {  # label, env, args...
     local label=$1 envs=$2; shift 2
     local json
-    json=$(env $envs python bench.py --query-len 256 --cand-len 256 --candidates "$N" --steps 32 --warmup 4 --extras off --traffic off --cpu-seconds 1 --settle-ms 100 "$@" 2>/dev/null | grep '^{' | tail -1)
+    json=$(env $envs python bench.py --query-len 256 --cand-len 256 --candidates "$N" --steps 32 --warmup 4 --full --extras off --traffic off --cpu-seconds 1 --settle-ms 100 "$@" 2>/dev/null | grep '^{' | tail -1)
     python - "$label" "$envs" "$json" "$@" >> "$OUT" <<'PY'
 import json, sys
 label, envs, js = sys.argv[1], sys.argv[2], sys.argv[3]

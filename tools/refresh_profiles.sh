@@ -1,11 +1,12 @@
 #!/bin/bash
-# Regenerates everything under profiles/ that comes from the GPU box (run through gpurun from the repo root):
+# Regenerates everything under profiles/ that comes from the GPU box (run from the repo root on an MI355X):
 #   rocprofv3 kernel-trace + PMC summaries of every BASELINE.json config's dominant kernel, and one bench.py JSON line per config.
-# Results land in gpurun_out/profiles/; copy them into profiles/ afterwards.
+# Results land in $OUT/profiles/ (OUT defaults to build/profiles_run); copy them into profiles/ afterwards.
 set -u
 R=${1:-r06}
-mkdir -p gpurun_out/profiles
-cp profiles/traffic.json gpurun_out/traffic.json 2>/dev/null
+export OUT=${OUT:-build/profiles_run}
+mkdir -p "$OUT/profiles"
+cp profiles/traffic.json "$OUT/traffic.json" 2>/dev/null
 # ONLY=<substring> restricts the run to the profiles / bench lines whose tag contains it (e.g. ONLY=ragged)
 # PROFILES="tag tag ..." restricts the rocprofv3 summaries (five passes each) to those tags; the bench lines always run
 P() { tag=$1; key=$2; shift 2; [[ -n "${ONLY:-}" && $tag != *$ONLY* ]] && return; [[ -n "${PROFILES:-}" && " $PROFILES " != *" $tag "* ]] && return; tools/profile_c2.sh ${tag}_$R "$key" "$@"; }
@@ -35,10 +36,10 @@ MATCH="rf::stream_lcs6" P ragged_indel_slots "none" --ragged --metric indel --sl
 MATCH="rf::band_list" P hint16_neardup90_band "none" --query-len 256 --cand-len 256 --candidates 10000000 --near-dup-share 0.9 --hint 16
 MATCH="sparse_words" P hint16_neardup90_sparse "none" --query-len 256 --cand-len 256 --candidates 10000000 --near-dup-share 0.9 --hint 16
 MATCH="rf::band_sparse" P c3_cutoff8_neardup1_sparse "none" --query-len 256 --cand-len 256 --candidates 10000000 --near-dup-share 0.01 --cutoff 8
-sed -i "s#gpurun_out/#profiles/#g" gpurun_out/traffic.json; cp gpurun_out/traffic.json gpurun_out/profiles/traffic.json
-b() { name=$1; shift; [[ -n "${ONLY:-}" && $name != *$ONLY* ]] && return; python bench.py --traffic off --extras off "$@" 2>/dev/null | tail -1 > gpurun_out/profiles/bench_$name.json; }
-# the default line exactly as the driver runs it (extra_configs legs, in-run traffic)
-[[ -z "${ONLY:-}" || c2_levenshtein == *$ONLY* ]] && python bench.py 2>/dev/null | tail -1 > gpurun_out/profiles/bench_c2_levenshtein.json
+sed -i "s#$OUT/#profiles/#g" "$OUT/traffic.json"; cp "$OUT/traffic.json" "$OUT/profiles/traffic.json"
+b() { name=$1; shift; [[ -n "${ONLY:-}" && $name != *$ONLY* ]] && return; python bench.py --full --traffic off --extras off "$@" 2>/dev/null | tail -1 > "$OUT/profiles/bench_$name.json"; }
+# the default workload with everything --full adds (extra_configs legs, in-run traffic)
+[[ -z "${ONLY:-}" || c2_levenshtein == *$ONLY* ]] && python bench.py --full 2>/dev/null | tail -1 > "$OUT/profiles/bench_c2_levenshtein.json"
 b ragged_cutoff3 --ragged --cutoff 3
 b ragged57_cutoff3 --ragged --min-len 57 --cutoff 3
 b ragged57_osa_cutoff3 --ragged --min-len 57 --cutoff 3 --metric osa --no-cpu-baseline
@@ -87,18 +88,18 @@ b ragged_jaro_winkler_slots --ragged --metric jaro_winkler --slot-order
 b ragged_lognormal_indel --ragged --metric indel --lognormal-median 24 --zipf 1.1
 b ragged57_filter_cutoff3 --ragged --min-len 57 --cutoff 3 --mode filter
 b jw_filter0.9 --metric jaro_winkler --fcutoff 0.9 --mode filter
-if [ -n "${ONLY:-}" ]; then cp gpurun_out/*_$R.txt gpurun_out/*_$R.json gpurun_out/profiles/ 2>/dev/null; ls gpurun_out/profiles | wc -l; exit 0; fi
-RF_BENCH_FORCE_DIST=1 python bench.py --steps 20 --no-cpu-baseline --traffic off --extras off 2>/dev/null | tail -1 > gpurun_out/profiles/bench_sharded_path_world1.json
-python bench.py --config c5 --extras off 2>/dev/null | tail -1 > gpurun_out/profiles/bench_c5_1B_world1.json
-python tools/time_mixed.py > gpurun_out/profiles/mixed_tiles_$R.txt 2>/dev/null; RF_NO_MIXED_TILES=1 python tools/time_mixed.py >> gpurun_out/profiles/mixed_tiles_$R.txt 2>/dev/null
-for v in lev256c8; do RF_NO_BAND=1 python tools/ab_time.py $v 2>/dev/null | tail -1 | sed 's/librfgpu.so/RF_NO_BAND=1/'; python tools/ab_time.py $v 2>/dev/null | tail -1; done > gpurun_out/profiles/band_ab_$R.txt
-for v in lev64 lev64+topk lev64+topk+out indel indel+topk jw; do python tools/ab_time.py $v 2>/dev/null | tail -1; done > gpurun_out/profiles/variants_$R.txt
+if [ -n "${ONLY:-}" ]; then cp "$OUT"/*_$R.txt "$OUT"/*_$R.json "$OUT/profiles/" 2>/dev/null; ls "$OUT/profiles" | wc -l; exit 0; fi
+RF_BENCH_FORCE_DIST=1 python bench.py --steps 20 --full --no-cpu-baseline --traffic off --extras off 2>/dev/null | tail -1 > "$OUT/profiles/bench_sharded_path_world1.json"
+python bench.py --config c5 --full --extras off 2>/dev/null | tail -1 > "$OUT/profiles/bench_c5_1B_world1.json"
+python tools/time_mixed.py > "$OUT"/profiles/mixed_tiles_$R.txt 2>/dev/null; RF_NO_MIXED_TILES=1 python tools/time_mixed.py >> "$OUT"/profiles/mixed_tiles_$R.txt 2>/dev/null
+for v in lev256c8; do RF_NO_BAND=1 python tools/ab_time.py $v 2>/dev/null | tail -1 | sed 's/librfgpu.so/RF_NO_BAND=1/'; python tools/ab_time.py $v 2>/dev/null | tail -1; done > "$OUT"/profiles/band_ab_$R.txt
+for v in lev64 lev64+topk lev64+topk+out indel indel+topk jw; do python tools/ab_time.py $v 2>/dev/null | tail -1; done > "$OUT"/profiles/variants_$R.txt
 # kernel timeline of the sharded step (top-16 + every distance + exchange), world size 1
 ( cd /tmp && RF_BENCH_FORCE_DIST=1 rocprofv3 --kernel-trace -d /tmp/kt_sh_$R -o kt -- python $OLDPWD/bench.py --steps 20 --warmup 5 --no-cpu-baseline --traffic off --extras off > /tmp/kt_sh_$R.log 2>&1 )
-( echo "sharded step at world size 1 (RF_BENCH_FORCE_DIST=1 python bench.py --steps 20 --warmup 5): rocprofv3 --kernel-trace, last two steps"; python tools/timeline.py /tmp/kt_sh_$R/kt_results.db 3 ) > gpurun_out/profiles/sharded_step_$R.txt
+( echo "sharded step at world size 1 (RF_BENCH_FORCE_DIST=1 python bench.py --steps 20 --warmup 5): rocprofv3 --kernel-trace, last two steps"; python tools/timeline.py /tmp/kt_sh_$R/kt_results.db 3 ) > "$OUT"/profiles/sharded_step_$R.txt
 # the clock ramp after an idle phase: per-launch duration of back-to-back plain scans with the settle phase off
 ( cd /tmp && rocprofv3 --kernel-trace -d /tmp/kt_ramp_$R -o kt -- python $OLDPWD/bench.py --steps 40 --warmup 0 --settle-ms 0 --no-cpu-baseline --traffic off --extras off > /tmp/kt_ramp_$R.log 2>&1 )
-python - > gpurun_out/profiles/clock_ramp_$R.txt <<PY
+python - > "$OUT"/profiles/clock_ramp_$R.txt <<PY
 import sqlite3
 cur = sqlite3.connect("/tmp/kt_ramp_$R/kt_results.db").cursor()
 d = [(e - s) / 1e3 for n, s, e in cur.execute("select name, start, end from kernels order by start") if ("stream_kernel" in n or "lev1_asm_kernel" in n or "stream_lev64" in n) and e - s > 1_000_000]
@@ -106,5 +107,5 @@ print("python bench.py --steps 40 --warmup 0 --settle-ms 0 under rocprofv3 --ker
 print(" ".join(f"{x:.0f}" for x in d))
 print(f"first 5 avg {sum(d[:5]) / 5:.0f} us; launches 20+ avg {sum(d[20:]) / max(1, len(d[20:])):.0f} us -> bench.py runs --settle-ms (default 200) of untimed steps before the W warm-up steps and reports config.settle_steps")
 PY
-cp gpurun_out/*_$R.txt gpurun_out/*_$R.json gpurun_out/profiles/ 2>/dev/null
-ls gpurun_out/profiles | wc -l
+cp "$OUT"/*_$R.txt "$OUT"/*_$R.json "$OUT/profiles/" 2>/dev/null
+ls "$OUT/profiles" | wc -l

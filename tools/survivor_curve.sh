@@ -9,7 +9,7 @@ N=${2:-100000000}
 line() {  # label, env, args...
     local label=$1 envs=$2; shift 2
     local json
-    json=$(env $envs python bench.py --candidates "$N" --steps 20 --warmup 3 --extras off --traffic off --cpu-seconds 1 --settle-ms 100 "$@" 2>/dev/null | grep '^{' | tail -1)
+    json=$(env $envs python bench.py --candidates "$N" --steps 20 --warmup 3 --full --extras off --traffic off --cpu-seconds 1 --settle-ms 100 "$@" 2>/dev/null | grep '^{' | tail -1)
     python - "$label" "$envs" "$json" "$@" >> "$OUT" <<'PY'
 import json, sys
 label, envs, js = sys.argv[1], sys.argv[2], sys.argv[3]
