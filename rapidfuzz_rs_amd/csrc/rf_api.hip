@@ -202,7 +202,6 @@ rf_status make_effective(const rf_comparator* c_in, const rf_corpus* corpus, hip
     bool overflow_hit = false;
     const rf_status rs = resolve(c_in, corpus, &e->c, &e->hold, &overflow_hit);
     e->corpus = corpus;
-    e->stream = st;
     if (rs == RF_OK || !overflow_hit || !corpus->d_raw) return rs;
 
     // query-local ids: 1, 2, ... in order of first appearance.  When the query has at most 255 distinct symbols that numbering does
@@ -280,12 +279,13 @@ rf_status make_effective(const rf_comparator* c_in, const rf_corpus* corpus, hip
         }
     }
     const size_t table_off = (corpus->data_bytes + 15) / 16 * 16;
-    RF_HIP(scratch_alloc((void**)&e->temp, table_off + (size_t)cap * 5, st));
-    uint32_t* d_keys = reinterpret_cast<uint32_t*>(e->temp + table_off);
+    uint8_t* temp = nullptr;
+    RF_HIP(e->scratch.get(&temp, table_off + (size_t)cap * 5));
+    uint32_t* d_keys = reinterpret_cast<uint32_t*>(temp + table_off);
     uint8_t* d_vals = reinterpret_cast<uint8_t*>(d_keys + cap);
     RF_HIP(hipMemcpyAsync(d_keys, e->keys.data(), (size_t)cap * 4, hipMemcpyHostToDevice, st));
     RF_HIP(hipMemcpyAsync(d_vals, e->vals.data(), cap, hipMemcpyHostToDevice, st));
-    const hipError_t le = launch_translate(corpus->d_raw, corpus->raw_elem, corpus->data_bytes, d_keys, d_vals, cap, e->temp, st);
+    const hipError_t le = launch_translate(corpus->d_raw, corpus->raw_elem, corpus->data_bytes, d_keys, d_vals, cap, temp, st);
     if (le != hipSuccess) {
         set_error(std::string("translate: ") + hipGetErrorString(le));
         return RF_ERR_HIP;
@@ -301,7 +301,7 @@ rf_status make_effective(const rf_comparator* c_in, const rf_corpus* corpus, hip
     v.n = corpus->n;
     v.payload_bytes = corpus->payload_bytes;
     v.data_bytes = corpus->data_bytes;
-    v.d_data = e->temp;
+    v.d_data = temp;
     v.d_tiles = corpus->d_tiles;
     v.d_orig = corpus->d_orig;
     v.n_tiles = corpus->n_tiles;
@@ -1304,21 +1304,13 @@ void rf_corpus_free(rf_corpus* c)
     if (c->d_tiles) (void)hipFree(c->d_tiles);
     if (c->d_tiles_by_origin) (void)hipFree(c->d_tiles_by_origin);
     if (c->d_orig) (void)hipFree(c->d_orig);
-    if (c->d_heads8) (void)hipFree(c->d_heads8);
-    if (c->d_heads6) (void)hipFree(c->d_heads6);
-    if (c->d_data6) (void)hipFree(c->d_data6);
-    if (c->d_slot_of) (void)hipFree(c->d_slot_of);
-    if (c->d_slot_ident) (void)hipFree(c->d_slot_ident);
-    if (c->d_window_table) (void)hipFree(c->d_window_table);
-    if (c->d_slot_off16) (void)hipFree(c->d_slot_off16);
-    if (c->d_len_of) (void)hipFree(c->d_len_of);
     if (c->d_mixed) (void)hipFree(c->d_mixed);
     if (c->d_mixed_len) (void)hipFree(c->d_mixed_len);
     if (c->d_mixed_orig) (void)hipFree(c->d_mixed_orig);
     if (c->d_sigma) (void)hipFree(c->d_sigma);
     if (c->d_raw) (void)hipFree(c->d_raw);
     if (c->d_sigma_identity) (void)hipFree(c->d_sigma_identity);
-    delete c;  // (and with it the per-stream caches)
+    delete c;  // (and with it the structures built on first use and the per-stream caches)
 }
 
 size_t rf_corpus_count(const rf_corpus* c) { return c->n; }
@@ -1328,19 +1320,12 @@ uint64_t rf_corpus_payload_bytes(const rf_corpus* c) { return c->payload_bytes; 
 uint64_t rf_corpus_device_bytes(const rf_corpus* c)
 {
     if (!c) return 0;
-    uint64_t aux = 0;
+    uint64_t accel = 0;
     {
         std::lock_guard<std::mutex> lock(c->scratch_mu);
-        if (c->d_heads8) aux += ((uint64_t)(c->uniform ? c->n_tiles : c->n_exact) + 1) * kWave * 8;
-        if (c->d_heads6) aux += ((uint64_t)(c->n_tiles + 1) / 2 + 1) * 3 * kWave * 4;
-        if (c->d_data6) aux += ((c->uniform ? (uint64_t)c->n_tiles * ((c->uniform_len + kChunk - 1) / kChunk) : c->data_bytes / (kWave * kChunk)) + 1) * kWave * 12;
-        if (c->d_slot_ident) aux += (uint64_t)c->n_slots * sizeof(uint32_t);
-        if (c->d_slot_of) aux += (uint64_t)c->n * sizeof(uint32_t);
-        if (c->d_window_table) aux += (uint64_t)c->gather_rows * c->gather_runs * sizeof(uint32_t);
-        if (c->d_slot_off16) aux += (uint64_t)c->n_slots * sizeof(uint16_t);
-        if (c->d_len_of) aux += (uint64_t)c->n * sizeof(uint32_t);
+        accel = c->accel.bytes();
     }
-    return c->device_bytes + aux + c->topk_scratch.bytes() + c->gather_tmp.bytes() + c->tile_lists.bytes();
+    return c->device_bytes + accel + c->topk_scratch.bytes() + c->gather_tmp.bytes() + c->tile_lists.bytes();
 }
 int rf_corpus_device(const rf_corpus* c) { return c->device; }
 size_t rf_corpus_alphabet_size(const rf_corpus* c, size_t* overflow_symbols)

@@ -18,21 +18,6 @@ extern "C" {
 
 namespace {
 
-struct ScratchSet {  // everything a call allocates, released in stream order on every way out
-    hipStream_t st;
-    std::vector<void*> blocks;
-    ~ScratchSet()
-    {
-        for (void* b : blocks) scratch_free(b, st);
-    }
-    hipError_t get(void** p, size_t bytes)
-    {
-        const hipError_t e = scratch_alloc(p, std::max<size_t>(bytes, 256), st);
-        if (e == hipSuccess) blocks.push_back(*p);
-        return e;
-    }
-};
-
 // What filter_small_kernel reports -- [0] results, [1] entries, [2] flag, [3] the call's sequence number -- lands in PINNED HOST memory the calling thread
 // spins on: no device-to-host copy command, no stream synchronization between the kernel's last store and the host seeing the count (measured on the
 // configs[4] shape at 100 M: 202 -> ~185 us per call; the count coming home is the one thing a filter call cannot enqueue and forget).  One 64-byte slot per
@@ -168,19 +153,19 @@ static rf_status run_filter(const rf_comparator* c, const rf_corpus* corpus, rf_
     const bool desc = op == RF_OP_SIMILARITY || op == RF_OP_NORMALIZED_SIMILARITY;
     const bool by_score = order == RF_FILTER_BY_SCORE;
     const uint32_t cap = (uint32_t)std::min<uint64_t>(capacity, corpus->n);
-    ScratchSet sc{st, {}};
+    ScratchSet sc(st);
     // where the caller's arrays are filled: in place (device memory) or in a device copy that goes home at the end
     uint64_t* d_index64 = out_index;
     void* d_score = out_score;
     if (out_mem == RF_MEM_HOST && cap) {
-        RF_HIP(sc.get((void**)&d_index64, (size_t)cap * sizeof(uint64_t)));
+        RF_HIP(sc.get(&d_index64, (size_t)cap * sizeof(uint64_t)));
         RF_HIP(sc.get(&d_score, (size_t)cap * elem));
     }
     // what the last kernel of a road reports: [0] results, [1] entries it saw, [2] 1 = too many for one workgroup, [4] an auxiliary device word -- into the calling
     // thread's pinned slot (the host spins on the sequence number) or, without pinned memory, into device words that are copied home behind a synchronization
     ResultSlot& slot = result_slot();
     uint32_t* d_res = nullptr;
-    if (!slot.host) RF_HIP(sc.get((void**)&d_res, 8 * sizeof(uint32_t)));
+    if (!slot.host) RF_HIP(sc.get(&d_res, 8 * sizeof(uint32_t)));
     auto report_target = [&]() { return slot.host ? (++slot.seq, const_cast<uint32_t*>(slot.host)) : d_res; };
     auto await_report = [&](uint32_t h[5]) -> rf_status {
         if (slot.host) {
@@ -205,14 +190,14 @@ static rf_status run_filter(const rf_comparator* c, const rf_corpus* corpus, rf_
     auto general = [&](const void* e_val, const uint32_t* e_map, uint32_t e_map_from, uint32_t e_bound, const uint32_t* e_dev, bool in_index_order, const uint32_t* aux_dev,
                        uint32_t h[5], const std::function<void()>& enqueued) -> rf_status {
         if (!d_idx) {
-            RF_HIP(sc.get((void**)&d_idx, (size_t)std::max(cap, 1u) * sizeof(uint32_t)));
+            RF_HIP(sc.get(&d_idx, (size_t)std::max(cap, 1u) * sizeof(uint32_t)));
             RF_HIP(sc.get(&d_val, (size_t)std::max(cap, 1u) * elem));
         }
         const uint32_t n_seg = filter_segments(e_bound);
         uint32_t* seg = nullptr;
         void* temp = nullptr;
         const size_t temp_bytes = filter_scan_temp_bytes(n_seg);
-        RF_HIP(sc.get((void**)&seg, ((size_t)n_seg + 1) * sizeof(uint32_t)));
+        RF_HIP(sc.get(&seg, ((size_t)n_seg + 1) * sizeof(uint32_t)));
         RF_HIP(sc.get(&temp, temp_bytes));
         RF_HIP(launch_filter_compact(e_val, f64_out, e_map, e_map_from, e_bound, e_dev, seg, temp, temp_bytes, cap, d_idx, d_val, st));
         const uint32_t* d_count = seg + n_seg;
@@ -249,7 +234,7 @@ static rf_status run_filter(const rf_comparator* c, const rf_corpus* corpus, rf_
         if (!in_index_order) {  // (by score too: ties go by index, and the sort by score is stable)
             uint32_t* idx2 = nullptr;
             void* val2 = nullptr;
-            RF_HIP(sc.get((void**)&idx2, (size_t)have * sizeof(uint32_t)));
+            RF_HIP(sc.get(&idx2, (size_t)have * sizeof(uint32_t)));
             RF_HIP(sc.get(&val2, (size_t)have * elem));
             RF_HIP(launch_filter_sort_by_index(idx_now, val_now, f64_out, have, idx2, val2, stemp, stemp_bytes, st));
             idx_now = idx2, val_now = val2;
@@ -257,7 +242,7 @@ static rf_status run_filter(const rf_comparator* c, const rf_corpus* corpus, rf_
         if (by_score) {
             uint32_t* idx3 = nullptr;
             void *key_in = nullptr, *key_out = nullptr;
-            RF_HIP(sc.get((void**)&idx3, (size_t)have * sizeof(uint32_t)));
+            RF_HIP(sc.get(&idx3, (size_t)have * sizeof(uint32_t)));
             RF_HIP(sc.get(&key_in, (size_t)have * sizeof(uint64_t)));
             RF_HIP(sc.get(&key_out, (size_t)have * sizeof(uint64_t)));
             RF_HIP(launch_filter_sort_by_score(idx_now, val_now, f64_out, desc, have, key_in, key_out, idx3, stemp, stemp_bytes, st));

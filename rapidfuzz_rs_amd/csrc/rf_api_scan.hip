@@ -381,37 +381,41 @@ struct AccelTimer {
     }
 };
 
+// Every member of rf_corpus::Accel is built the same way, by its caller under scratch_mu: fill(local owner) enqueues the build, the stream
+// is synchronized before the lock is released (other streams may use the structure from then on), and only then is the owner published
+// into `slot` by move.  On failure the HIP error is cleared, the local owner frees itself and `slot` is untouched.
+extern "C++" template <class T, class Fill>
+static void accel_build(T& slot, const char* what, hipStream_t st, Fill&& fill)
+{
+    AccelTimer timer(what);
+    T local{};
+    hipError_t e = fill(local);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) slot = std::move(local);
+    else (void)hipGetLastError();
+}
+
 // The largest stored symbol of the payload (symbols are stored as their frequency rank: a 62-symbol corpus holds 0 .. 61), computed
 // exactly on first use -- one streaming pass -- and kept.  0xFFFFFFFF when it cannot be had.
 static uint32_t corpus_max_stored_symbol(const rf_corpus* corpus, hipStream_t st)
 {
     if (corpus->borrowed || corpus->wide || !corpus->d_data || corpus->data_bytes < 16) return 0xFFFFFFFFu;
     std::lock_guard<std::mutex> lock(corpus->scratch_mu);
-    if (corpus->max_stored_sym == 0xFFFFFFFFu) {
-        AccelTimer timer("largest stored symbol");
-        uint32_t* d = nullptr;
-        uint32_t v = 0;
-        if (hipMalloc((void**)&d, sizeof(uint32_t)) != hipSuccess) {
-            (void)hipGetLastError();
-            return 0xFFFFFFFFu;
-        }
-        hipError_t e = hipMemsetAsync(d, 0, sizeof(uint32_t), st);
-        if (e == hipSuccess) e = launch_max_byte(corpus->d_data, corpus->data_bytes, d, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(&v, d, sizeof(uint32_t), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        (void)hipFree(d);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return 0xFFFFFFFFu;
-        }
-        corpus->max_stored_sym = v;
-    }
-    return corpus->max_stored_sym;
+    uint32_t& v = corpus->accel.max_stored_sym;
+    DeviceBuf d;
+    if (v == 0xFFFFFFFFu)
+        accel_build(v, "largest stored symbol", st, [&](uint32_t& m) {
+            hipError_t e = d.reserve(sizeof(uint32_t));
+            if (e == hipSuccess) e = hipMemsetAsync(d.ptr, 0, sizeof(uint32_t), st);
+            if (e == hipSuccess) e = launch_max_byte(corpus->d_data, corpus->data_bytes, d.as<uint32_t>(), st);
+            return e == hipSuccess ? hipMemcpyAsync(&m, d.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost, st) : e;
+        });
+    return v;
 }
 
 // Small-cutoff Levenshtein scans of large single-length corpora take their first look from the head plane (rf_pack.hip
 // head8_plane_kernel).  Built once per corpus, on the first such scan; RF_HEAD8_MIN=<tiles> moves the threshold (0 = never).
-// Failing to allocate it is not an error: the scan then reads the tiles' first chunk rows as before.
+// Failing to allocate it is not an error: the scan then reads the tiles' first chunk rows as before (the next call tries again).
 const uint8_t* corpus_head8_plane(const rf_corpus* corpus, const ScanParams& p, RawKind raw, hipStream_t st)
 {
     static const size_t min_tiles = [] { const char* e = getenv("RF_HEAD8_MIN"); return e ? (size_t)atoll(e) : (size_t)1 << 14; }();
@@ -423,60 +427,43 @@ const uint8_t* corpus_head8_plane(const rf_corpus* corpus, const ScanParams& p, 
     if (plane_tiles < min_tiles || (corpus->uniform ? corpus->uniform_len < (uint32_t)kChunk : (!corpus->d_tiles || !corpus->d_orig || corpus->max_len < (uint32_t)kChunk)))
         return nullptr;
     std::lock_guard<std::mutex> lock(corpus->scratch_mu);
-    if (!corpus->d_heads8) {
-        AccelTimer timer("head plane (8 symbols)");
-        uint8_t* h = nullptr;
-        if (hipMalloc((void**)&h, ((size_t)plane_tiles + 1) * kWave * 8) != hipSuccess) {  // (+ one row: head_filter_kernel reads tiles in pairs)
-            (void)hipGetLastError();
-            return nullptr;
-        }
-        hipError_t e = corpus->uniform ? launch_head8_plane(corpus->d_data, corpus->n_tiles, (uint32_t)tile_bytes(corpus->uniform_len), h, st)
-                                       : launch_head8_plane_tiles(corpus->d_data, corpus->d_tiles, plane_tiles, h, st);
-        if (e == hipSuccess) e = hipMemsetAsync(h + (size_t)plane_tiles * kWave * 8, 0, kWave * 8, st);  // the pad row: defined bytes
-        if (e == hipSuccess) e = hipStreamSynchronize(st);  // (other streams may use the plane as soon as the lock is released)
-        if (e != hipSuccess) {
-            (void)hipFree(h);
-            return nullptr;
-        }
-        corpus->d_heads8 = h;
-    }
-    return corpus->d_heads8;
+    DeviceBuf& plane = corpus->accel.heads8;
+    if (!plane.ptr)
+        accel_build(plane, "head plane (8 symbols)", st, [&](DeviceBuf& h) {
+            hipError_t e = h.reserve(((size_t)plane_tiles + 1) * kWave * 8);  // (+ one row: head_filter_kernel reads tiles in pairs)
+            if (e == hipSuccess)
+                e = corpus->uniform ? launch_head8_plane(corpus->d_data, corpus->n_tiles, (uint32_t)tile_bytes(corpus->uniform_len), h.as<uint8_t>(), st)
+                                    : launch_head8_plane_tiles(corpus->d_data, corpus->d_tiles, plane_tiles, h.as<uint8_t>(), st);
+            return e == hipSuccess ? hipMemsetAsync(h.as<uint8_t>() + (size_t)plane_tiles * kWave * 8, 0, kWave * 8, st) : e;  // the pad row: defined bytes
+        });
+    return plane.as<uint8_t>();
 }
 
 // The head plane at 6 bits per symbol (ScanParams::heads6): single-length corpora whose payload holds no stored symbol above 63 -- the
 // band prefilter pass then streams 6 instead of 8 bytes per candidate.  Built from the 8-byte plane on first use, kept beside it
-// (+ 6 bytes per candidate); RF_HEAD6=0 switches it off.  nullptr = not to be had.
+// (+ 6 bytes per candidate); RF_HEAD6=0 switches it off.  nullptr = not to be had (tried once).
 const uint32_t* corpus_head6_plane(const rf_corpus* corpus, hipStream_t st)
 {
     static const bool on = [] { const char* e = getenv("RF_HEAD6"); return !e || atoi(e) != 0; }();
-    if (!on || !corpus->uniform || !corpus->d_heads8 || corpus->borrowed) return nullptr;
+    if (!on || !corpus->uniform || !corpus->accel.heads8.ptr || corpus->borrowed) return nullptr;
     if (corpus_max_stored_symbol(corpus, st) >= 64u) return nullptr;
     std::lock_guard<std::mutex> lock(corpus->scratch_mu);
-    if (!corpus->d_heads6 && !corpus->heads6_tried) {
-        corpus->heads6_tried = true;
-        AccelTimer timer("head plane at 6 bits");
-        uint32_t* h = nullptr;
+    rf_corpus::Accel& a = corpus->accel;
+    if (!a.heads6.ptr && !a.heads6_tried) {
+        a.heads6_tried = true;
         const size_t rows = ((size_t)corpus->n_tiles + 1) / 2 + 1;  // (+ one pair: the pass reads a pair ahead)
-        if (hipMalloc((void**)&h, rows * 3 * kWave * sizeof(uint32_t)) != hipSuccess) {
-            (void)hipGetLastError();
-            return nullptr;
-        }
-        hipError_t e = launch_head6_plane(corpus->d_heads8, corpus->n_tiles, h, st);
-        if (e == hipSuccess) e = hipMemsetAsync(h + (rows - 1) * 3 * kWave, 0, 3 * kWave * sizeof(uint32_t), st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);  // (other streams may use the plane as soon as the lock is released)
-        if (e != hipSuccess) {
-            (void)hipFree(h);
-            (void)hipGetLastError();
-            return nullptr;
-        }
-        corpus->d_heads6 = h;
+        accel_build(a.heads6, "head plane at 6 bits", st, [&](DeviceBuf& h) {
+            hipError_t e = h.reserve(rows * 3 * kWave * sizeof(uint32_t));
+            if (e == hipSuccess) e = launch_head6_plane(a.heads8.as<uint8_t>(), corpus->n_tiles, h.as<uint32_t>(), st);
+            return e == hipSuccess ? hipMemsetAsync(h.as<uint32_t>() + (rows - 1) * 3 * kWave, 0, 3 * kWave * sizeof(uint32_t), st) : e;
+        });
     }
-    return corpus->d_heads6;
+    return a.heads6.as<uint32_t>();
 }
 
 // The payload at 6 bits per symbol (ScanParams::data6, rf_pack.hip pack6_kernel): single-length corpora whose payload holds no stored symbol above 63
 // (exact: corpus_max_stored_symbol) and at least RF_PACK6_MIN_TILES tiles (default 16384: a scan that does not fill the chip is not HBM-bound).  Built
-// from the 8-bit payload on first use by a scan that streams it, kept beside it (+ 75 % of the payload in HBM); RF_PACK6=0 switches it off.
+// from the 8-bit payload on first use by a scan that streams it (tried once), kept beside it (+ 75 % of the payload in HBM); RF_PACK6=0 switches it off.
 const uint32_t* corpus_data6(const rf_corpus* corpus, hipStream_t st)
 {
     static const bool on = [] { const char* e = getenv("RF_PACK6"); return !e || atoi(e) != 0; }();
@@ -487,30 +474,85 @@ const uint32_t* corpus_data6(const rf_corpus* corpus, hipStream_t st)
     // scans shift a partial chunk into place like the 8-bit kernels do, any 64 codes)
     if (corpus_max_stored_symbol(corpus, st) >= ((!corpus->uniform || corpus->uniform_len % kChunk == 0) ? 64u : 63u)) return nullptr;
     std::lock_guard<std::mutex> lock(corpus->scratch_mu);
-    if (!corpus->d_data6 && !corpus->data6_tried) {
-        corpus->data6_tried = true;
-        AccelTimer timer("6-bit payload");
+    rf_corpus::Accel& a = corpus->accel;
+    if (!a.data6.ptr && !a.data6_tried) {
+        a.data6_tried = true;
         // chunk rows of 64 lanes: tiles x chunks of a single-length corpus; a bucketed one's whole payload, row by row (the 6-bit image mirrors it at 3/4 of every offset)
         const uint32_t nch = corpus->uniform ? (corpus->uniform_len + kChunk - 1) / kChunk : 1;
         const uint64_t rows = corpus->uniform ? (uint64_t)corpus->n_tiles * nch : corpus->data_bytes / (kWave * kChunk);
         if (rows * kWave >= 0xFFFFFFFFull) return nullptr;
-        uint32_t* d = nullptr;
-        if (hipMalloc((void**)&d, (rows + 1) * kWave * 12) != hipSuccess) {  // (+ one chunk row: the scans prefetch past the last tile)
-            (void)hipGetLastError();
-            return nullptr;
-        }
-        hipError_t e = corpus->uniform ? launch_pack6(corpus->d_data, corpus->n_tiles, corpus->uniform_len, d, st)
-                                       : launch_pack6(corpus->d_data, (uint32_t)rows, (uint32_t)kChunk, d, st);  // (rows of one whole chunk each: nothing to fill)
-        if (e == hipSuccess) e = hipMemsetAsync(d + rows * kWave * 3, 0, kWave * 12, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);  // (other streams may use it as soon as the lock is released)
-        if (e != hipSuccess) {
-            (void)hipFree(d);
-            (void)hipGetLastError();
-            return nullptr;
-        }
-        corpus->d_data6 = d;
+        accel_build(a.data6, "6-bit payload", st, [&](DeviceBuf& d) {
+            hipError_t e = d.reserve((rows + 1) * kWave * 12);  // (+ one chunk row: the scans prefetch past the last tile)
+            if (e == hipSuccess)
+                e = corpus->uniform ? launch_pack6(corpus->d_data, corpus->n_tiles, corpus->uniform_len, d.as<uint32_t>(), st)
+                                    : launch_pack6(corpus->d_data, (uint32_t)rows, (uint32_t)kChunk, d.as<uint32_t>(), st);  // (rows of one whole chunk each: nothing to fill)
+            return e == hipSuccess ? hipMemsetAsync(d.as<uint32_t>() + rows * kWave * 3, 0, kWave * 12, st) : e;
+        });
     }
-    return corpus->d_data6;
+    return a.data6.as<uint32_t>();
+}
+
+// The candidates' lengths in original order, 4 bytes each, of a length-bucketed corpus (the normalizing pass of run_many_two_step), built once
+// from the tile descriptors on first use.  nullptr: no room (not an error: run_many's compiled f64 scan, same values); the next call tries again.
+static const uint32_t* corpus_len_of(const rf_corpus* corpus, hipStream_t st)
+{
+    std::lock_guard<std::mutex> lock(corpus->scratch_mu);
+    DeviceBuf& len_of = corpus->accel.len_of;
+    if (!len_of.ptr)
+        accel_build(len_of, "candidate lengths", st, [&](DeviceBuf& l) {
+            const hipError_t e = l.reserve(corpus->n * sizeof(uint32_t));
+            return e == hipSuccess ? launch_len_of(corpus->d_tiles, corpus->n_tiles, corpus->d_orig, l.as<uint32_t>(), st) : e;
+        });
+    return len_of.as<uint32_t>();
+}
+
+// The gather path's maps (rf_corpus::GatherMaps), built once per corpus on first use: the slot -> slot map the scans store through, and what
+// the gather needs -- the window table (rf_pack.hip window_gather_kernel) when the slots are few enough ascending runs, else the candidate ->
+// slot map.  Published together or not at all.  nullptr: no room -- not an error: an HBM-tight caller keeps what round 2 gave it,
+// the launch stores straight through orig[] (scattered, slower, same values).  The next call tries again.
+static const rf_corpus::GatherMaps* corpus_gather_maps(const rf_corpus* corpus, hipStream_t st)
+{
+    static const bool use_windows = [] { const char* e = getenv("RF_GATHER_WINDOWS"); return !e || atoi(e) != 0; }();
+    // (round 5) the window gather reads a slot's place inside its span from 2 bytes instead of the 4 of orig[] (RF_GATHER_OFF16=0: the A/B switch;
+    // no room for them: the gather reads orig[] as before)
+    static const bool use_off16 = [] { const char* e = getenv("RF_GATHER_OFF16"); return !e || atoi(e) != 0; }();
+    std::lock_guard<std::mutex> lock(corpus->scratch_mu);
+    rf_corpus::GatherMaps& maps = corpus->accel.gather;
+    const uint32_t n_slots = (uint32_t)corpus->n_slots;
+    if (!maps.slot_ident.ptr) {
+        DeviceBuf list;
+        std::vector<uint32_t> runs(kMaxGatherRuns + 2, 0u);  // [0] = count, then the run starts
+        accel_build(maps, "slot maps + window table", st, [&](rf_corpus::GatherMaps& m) {
+            hipError_t e = m.slot_ident.reserve(corpus->n_slots * sizeof(uint32_t));
+            if (e == hipSuccess && use_windows) {
+                e = list.reserve(runs.size() * sizeof(uint32_t));
+                if (e == hipSuccess) e = hipMemsetAsync(list.ptr, 0, sizeof(uint32_t), st);
+                if (e == hipSuccess) e = launch_run_starts(corpus->d_orig, n_slots, list.as<uint32_t>() + 1, kMaxGatherRuns, list.as<uint32_t>(), st);
+                if (e == hipSuccess) e = hipMemcpyAsync(runs.data(), list.ptr, (kMaxGatherRuns + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
+                if (e == hipSuccess) e = hipStreamSynchronize(st);
+                if (e == hipSuccess && runs[0] >= 1 && runs[0] <= kMaxGatherRuns) {
+                    m.runs = runs[0];
+                    std::sort(runs.begin() + 1, runs.begin() + 1 + m.runs);
+                    runs[1 + m.runs] = n_slots;
+                    m.rows = (uint32_t)((corpus->n + kGatherWindow - 1) / kGatherWindow) + 1;
+                    e = hipMemcpyAsync(list.ptr, runs.data() + 1, (m.runs + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+                    if (e == hipSuccess) e = m.window_table.reserve((size_t)m.rows * m.runs * sizeof(uint32_t));
+                    if (e == hipSuccess) e = launch_window_table(corpus->d_orig, list.as<uint32_t>(), m.runs, m.rows, m.window_table.as<uint32_t>(), st);
+                }
+            }
+            if (e == hipSuccess && !m.window_table.ptr) {
+                e = m.slot_of.reserve(corpus->n * sizeof(uint32_t));
+                if (e == hipSuccess) e = hipMemsetAsync(m.slot_of.ptr, 0xFF, corpus->n * sizeof(uint32_t), st);
+            }
+            if (e == hipSuccess) e = launch_slot_maps(corpus->d_orig, n_slots, m.slot_of.as<uint32_t>(), m.slot_ident.as<uint32_t>(), st);
+            if (e == hipSuccess && m.window_table.ptr && use_off16) {
+                if (m.slot_off16.reserve(corpus->n_slots * sizeof(uint16_t)) != hipSuccess) (void)hipGetLastError();
+                else e = launch_slot_off16(corpus->d_orig, n_slots, m.slot_off16.as<uint16_t>(), st);
+            }
+            return e;
+        });
+    }
+    return maps.slot_ident.ptr ? &maps : nullptr;
 }
 
 // The BAND PREFILTER of the head-plane cutoff scans (rf_scan.hip early_lean_body has the kernel side and the proof): with at most
@@ -755,6 +797,33 @@ static hipError_t launch_band_runs(RawKind raw, const ScanParams& p, const rf_co
     return e;
 }
 
+// The normalizing two-step of run_many (its comment has the why): the u32 distance scan under `raw_cut` into a temporary, then launch_normalize.
+// *taken = false: no room for the candidates' lengths or the temporaries -- not an error: run_many's compiled f64 scan needs none, same values.
+static rf_status run_many_two_step(const rf_comparator* c_in, const rf_corpus* corpus, const ScanParams& p, const rf_args* args, uint64_t raw_cut, double* out,
+                                   rf_mem out_mem, hipStream_t st, bool* taken)
+{
+    *taken = false;
+    const uint32_t* len_of = corpus->uniform ? nullptr : corpus_len_of(corpus, st);
+    if (!corpus->uniform && !len_of) return RF_OK;
+    ScratchSet sc(st);
+    uint32_t* d_dist = nullptr;
+    double* d_out = out;
+    if (sc.get(&d_dist, corpus->n * sizeof(uint32_t)) != hipSuccess || (out_mem == RF_MEM_HOST && sc.get(&d_out, corpus->n * sizeof(double)) != hipSuccess)) {
+        (void)hipGetLastError();
+        return RF_OK;
+    }
+    *taken = true;
+    rf_args a = *args;
+    a.cutoff_usize = raw_cut;  // (RF_NO_CUTOFF unless the f64 cutoff leaves <= 31 raw edits)
+    a.score_hint_usize = RF_NO_CUTOFF;
+    const rf_status rs = run_many(c_in, corpus, RF_OP_DISTANCE, &a, d_dist, RF_MEM_DEVICE, st, false);
+    if (rs != RF_OK) return rs;
+    hipError_t e = launch_normalize(d_dist, len_of, corpus->uniform_len, d_out, (uint32_t)corpus->n, p.len1, p.fin_mS, p.fin_mM, p.op, p.has_cutoff, p.cutoff_f64, st);
+    if (e == hipSuccess && out_mem == RF_MEM_HOST) e = copy_home(out, d_out, corpus->n * sizeof(double), st);
+    RF_HIP(e);
+    return RF_OK;
+}
+
 rf_status run_many(const rf_comparator* c_in, const rf_corpus* corpus_in, rf_op op, const rf_args* args, void* out, rf_mem out_mem, void* stream, bool f64_out);
 // score_hint on a per-candidate scan of a long query (reference: levenshtein.rs:1069-1088, the band of max(hint, 31) doubled until the
 // distance fits -- results never depend on the hint, :2153-2160).  rf_hint.hip has the scheme: pass 1 over everything under the cutoff k1 = max(hint, 31)
@@ -784,23 +853,9 @@ static rf_status run_many_hinted(const rf_comparator* c_in, const rf_corpus* cor
 {
     const rf_op op = RF_OP_DISTANCE;
     const size_t out_bytes = corpus->n * sizeof(uint32_t);
-    // everything this call allocates, released in stream order on every way out
-    struct Scratch {
-        hipStream_t st;
-        std::vector<void*> blocks;
-        ~Scratch()
-        {
-            for (void* b : blocks) scratch_free(b, st);
-        }
-        hipError_t get(void** p, size_t bytes)
-        {
-            const hipError_t e = scratch_alloc(p, bytes, st);
-            if (e == hipSuccess) blocks.push_back(*p);
-            return e;
-        }
-    } sc{st, {}};
+    ScratchSet sc(st);
     uint32_t* d_out = out;
-    if (out_mem == RF_MEM_HOST) RF_HIP(sc.get((void**)&d_out, out_bytes));
+    if (out_mem == RF_MEM_HOST) RF_HIP(sc.get(&d_out, out_bytes));
     rf_args a1 = *args;  // pass 1: everything under the cutoff k1 (in result units: times the common factor)
     a1.score_hint_usize = RF_NO_CUTOFF;
     a1.cutoff_usize = (uint64_t)k1 * factor;
@@ -832,7 +887,7 @@ static rf_status run_many_hinted(const rf_comparator* c_in, const rf_corpus* cor
             p1.heads8 = nullptr, p1.heads6 = nullptr;
             p1.tile_step = std::max<uint32_t>(1, (p1.tile_end - p1.tile_begin) / 512);
             uint32_t* d_acc = nullptr;
-            RF_HIP(sc.get((void**)&d_acc, 2 * sizeof(uint32_t)));
+            RF_HIP(sc.get(&d_acc, 2 * sizeof(uint32_t)));
             RF_HIP(hipMemsetAsync(d_acc, 0, 2 * sizeof(uint32_t), st));
             RF_HIP(launch_scan(raw1, p1, st, nullptr));
             RF_HIP(launch_hint_sample(p1, d_out, p1.tile_begin, p1.tile_end, p1.tile_step, d_acc, st));
@@ -856,10 +911,7 @@ static rf_status run_many_hinted(const rf_comparator* c_in, const rf_corpus* cor
                 corpus->hint_trust.store(0, std::memory_order_relaxed);
                 const rf_status rs = run_many(c_in, corpus_in, op, &a2, d_out, RF_MEM_DEVICE, st, false);
                 if (rs != RF_OK) return rs;
-                if (out_mem == RF_MEM_HOST) {
-                    RF_HIP(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st));
-                    RF_HIP(hipStreamSynchronize(st));
-                }
+                if (out_mem == RF_MEM_HOST) RF_HIP(copy_home(out, d_out, out_bytes, st));
                 return RF_OK;
             }
         }
@@ -910,10 +962,7 @@ static rf_status run_many_hinted(const rf_comparator* c_in, const rf_corpus* cor
                 corpus->hint_trust.store(std::min<uint32_t>(trust + 1, 0x7FFFFFFFu), std::memory_order_relaxed);
                 static const bool trace_lists = getenv("RF_TRACE_PLAN") != nullptr;
                 if (trace_lists) std::fprintf(stderr, "[rf plan] hint lists: k1=%u, the band pass lists what it leaves, %u-word scan over the list\n", k1, p2.words);
-                if (out_mem == RF_MEM_HOST) {
-                    RF_HIP(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st));
-                    RF_HIP(hipStreamSynchronize(st));
-                }
+                if (out_mem == RF_MEM_HOST) RF_HIP(copy_home(out, d_out, out_bytes, st));
                 return RF_OK;
             }
         }
@@ -935,11 +984,11 @@ static rf_status run_many_hinted(const rf_comparator* c_in, const rf_corpus* cor
     uint64_t* d_mask = nullptr;
     void* d_temp = nullptr;
     const size_t temp_bytes = hint_scan_temp_bytes(corpus->n_tiles);
-    RF_HIP(sc.get((void**)&d_run_first, (R + 1) * sizeof(uint32_t)));
-    RF_HIP(sc.get((void**)&d_run_prefix, (R + 1) * sizeof(uint32_t)));
-    RF_HIP(sc.get((void**)&d_count, ((size_t)corpus->n_tiles + 1) * sizeof(uint32_t)));
-    RF_HIP(sc.get((void**)&d_prefix, ((size_t)corpus->n_tiles + 1) * sizeof(uint32_t)));
-    RF_HIP(sc.get((void**)&d_mask, (size_t)corpus->n_tiles * sizeof(uint64_t)));
+    RF_HIP(sc.get(&d_run_first, (R + 1) * sizeof(uint32_t)));
+    RF_HIP(sc.get(&d_run_prefix, (R + 1) * sizeof(uint32_t)));
+    RF_HIP(sc.get(&d_count, ((size_t)corpus->n_tiles + 1) * sizeof(uint32_t)));
+    RF_HIP(sc.get(&d_prefix, ((size_t)corpus->n_tiles + 1) * sizeof(uint32_t)));
+    RF_HIP(sc.get(&d_mask, (size_t)corpus->n_tiles * sizeof(uint64_t)));
     RF_HIP(sc.get(&d_temp, temp_bytes));
     RF_HIP(hipMemcpyAsync(d_run_first, run_first.data(), (R + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     RF_HIP(launch_hint_mark(p, d_out, raw_cut, zero_value, d_mask, d_count, d_prefix, d_temp, temp_bytes, d_run_first, R, d_run_prefix, st));
@@ -982,12 +1031,12 @@ static rf_status run_many_hinted(const rf_comparator* c_in, const rf_corpus* cor
         std::memcpy(tables.data(), data_base.data(), R * sizeof(uint64_t));
         std::memcpy(reinterpret_cast<uint32_t*>(tables.data() + R), tile_base.data(), (R + 1) * sizeof(uint32_t));
         std::memcpy(reinterpret_cast<uint32_t*>(tables.data() + R) + (R + 1), run_len.data(), R * sizeof(uint32_t));
-        RF_HIP(sc.get((void**)&d_data_base, tables.size() * sizeof(uint64_t)));
+        RF_HIP(sc.get(&d_data_base, tables.size() * sizeof(uint64_t)));
         d_tile_base = reinterpret_cast<uint32_t*>(d_data_base + R);
         d_run_len = d_tile_base + (R + 1);
-        RF_HIP(sc.get((void**)&d_data2, bytes2 + kTailPad));
-        RF_HIP(sc.get((void**)&d_tiles2, (size_t)n_tiles2 * sizeof(TileDesc)));
-        RF_HIP(sc.get((void**)&d_orig2, (size_t)n_tiles2 * kWave * sizeof(uint32_t)));
+        RF_HIP(sc.get(&d_data2, bytes2 + kTailPad));
+        RF_HIP(sc.get(&d_tiles2, (size_t)n_tiles2 * sizeof(TileDesc)));
+        RF_HIP(sc.get(&d_orig2, (size_t)n_tiles2 * kWave * sizeof(uint32_t)));
         RF_HIP(hipMemcpyAsync(d_data_base, tables.data(), tables.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
         RF_HIP(hipMemsetAsync(d_data2 + bytes2, 0, kTailPad, st));  // (the scans prefetch one chunk row past the last tile)
         RF_HIP(launch_hint_gather(p, d_run_first, R, d_run_prefix, d_prefix, d_mask, d_tile_base, d_data_base, d_run_len, n_tiles2, d_data2, d_tiles2, d_orig2, st));
@@ -1008,14 +1057,11 @@ static rf_status run_many_hinted(const rf_comparator* c_in, const rf_corpus* cor
         p.out = d_out;
         if (p.long_words_pad) {  // (queries beyond 512 symbols: the multi-sweep kernel's scratch strips, sized for the dense tiles)
             p.long_grid = (uint32_t)std::max(1, std::min<int>((int)p.long_grid, scan_grid(n_tiles2)));
-            if (const size_t scratch = launch_scratch_bytes(p, raw)) RF_HIP(sc.get((void**)&p.long_scratch, scratch));
+            if (const size_t scratch = launch_scratch_bytes(p, raw)) RF_HIP(sc.get(&p.long_scratch, scratch));
         }
         RF_HIP(launch_scan(raw, p, st, nullptr));
     }
-    if (out_mem == RF_MEM_HOST) {
-        RF_HIP(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st));
-        RF_HIP(hipStreamSynchronize(st));
-    }
+    if (out_mem == RF_MEM_HOST) RF_HIP(copy_home(out, d_out, out_bytes, st));
     return RF_OK;
 }
 
@@ -1027,7 +1073,7 @@ rf_status run_many(const rf_comparator* c_in, const rf_corpus* corpus_in, rf_op 
         return RF_ERR_INVALID_ARG;
     }
     AccelTimer call_timer("rf_many call (host side)");
-    Effective eff;
+    Effective eff((hipStream_t)stream);
     if (const rf_status rs = make_effective(c_in, corpus_in, (hipStream_t)stream, &eff); rs != RF_OK) return rs;
     const rf_comparator* c = eff.c;
     const rf_corpus* corpus = eff.corpus;
@@ -1078,51 +1124,9 @@ rf_status run_many(const rf_comparator* c_in, const rf_corpus* corpus_in, rf_op 
     }
     if (norm_two_step && !want_slots && f64_out && raw == RAW_LEV && p.words >= 2 && p.words <= kMaxWords && (!p.early || norm_raw_cut != RF_NO_CUTOFF) && !p.long_words_pad && corpus == corpus_in && !corpus->borrowed &&
         corpus->n_tiles >= 16 && (uint64_t)p.len1 + corpus->max_len < 0x7FFFFFFFu && (corpus->uniform || (corpus->d_orig && corpus->d_tiles))) {
-        // (length-bucketed corpora: the candidates' lengths in original order, 4 bytes each, built once per corpus from the tile descriptors)
-        const uint32_t* len_of = nullptr;
-        if (!corpus->uniform) {
-            std::lock_guard<std::mutex> lock(corpus->scratch_mu);
-            if (!corpus->d_len_of) {
-                uint32_t* l = nullptr;
-                hipError_t e1 = hipMalloc((void**)&l, corpus->n * sizeof(uint32_t));
-                if (e1 == hipSuccess) e1 = launch_len_of(corpus->d_tiles, corpus->n_tiles, corpus->d_orig, l, st);
-                if (e1 == hipSuccess) e1 = hipStreamSynchronize(st);  // (other streams may use it as soon as the lock is released)
-                if (e1 != hipSuccess) {
-                    if (l) (void)hipFree(l);
-                    (void)hipGetLastError();  // (no room: the compiled f64 scan below, same values)
-                } else
-                    corpus->d_len_of = l;
-            }
-            len_of = corpus->d_len_of;
-        }
-        if (corpus->uniform || len_of) {
-            rf_args a = *args;
-            a.cutoff_usize = norm_raw_cut;  // (RF_NO_CUTOFF unless the f64 cutoff leaves <= 31 raw edits)
-            a.score_hint_usize = RF_NO_CUTOFF;
-            // (the temporaries are optional -- no room for them is not an error, the compiled f64 scan below needs none: same values)
-            uint32_t* d_dist = nullptr;
-            double* d_out = static_cast<double*>(out);
-            bool have_tmp = scratch_alloc((void**)&d_dist, corpus->n * sizeof(uint32_t), st) == hipSuccess;
-            if (have_tmp && out_mem == RF_MEM_HOST && scratch_alloc((void**)&d_out, corpus->n * sizeof(double), st) != hipSuccess) {
-                scratch_free(d_dist, st);
-                have_tmp = false;
-            }
-            if (!have_tmp) (void)hipGetLastError();
-          if (have_tmp) {
-            const rf_status rs = run_many(c_in, corpus_in, RF_OP_DISTANCE, &a, d_dist, RF_MEM_DEVICE, st, false);
-            hipError_t e = hipSuccess;
-            if (rs == RF_OK) e = launch_normalize(d_dist, len_of, corpus->uniform_len, d_out, (uint32_t)corpus->n, p.len1, p.fin_mS, p.fin_mM, p.op, p.has_cutoff, p.cutoff_f64, st);
-            scratch_free(d_dist, st);
-            if (rs == RF_OK && e == hipSuccess && out_mem == RF_MEM_HOST) {
-                e = hipMemcpyAsync(out, d_out, corpus->n * sizeof(double), hipMemcpyDeviceToHost, st);
-                if (e == hipSuccess) e = hipStreamSynchronize(st);
-            }
-            if (out_mem == RF_MEM_HOST && d_out != out) scratch_free(d_out, st);
-            if (rs != RF_OK) return rs;
-            RF_HIP(e);
-            return RF_OK;
-          }
-        }
+        bool taken = false;
+        const rf_status rs = run_many_two_step(c_in, corpus, p, args, norm_raw_cut, static_cast<double*>(out), out_mem, st, &taken);
+        if (taken) return rs;
     }
     {
         uint32_t k1 = 0, factor = 1;
@@ -1150,8 +1154,9 @@ rf_status run_many(const rf_comparator* c_in, const rf_corpus* corpus_in, rf_op 
     if (jaro_priv && raw == RAW_JARO && corpus->uniform && !p.has_cutoff) p.max_stored_sym = corpus_max_stored_symbol(corpus, st);
     const size_t elem = f64_out ? sizeof(double) : sizeof(uint32_t);
     const size_t out_bytes = (want_slots ? corpus->n_slots : corpus->n) * elem;
+    ScratchSet sc(st);
     void* d_out = out;
-    if (out_mem == RF_MEM_HOST) RF_HIP(scratch_alloc(&d_out, out_bytes, st));  // (kept by the pool: no hipMalloc / hipFree pair -- and no device-wide sync -- per call)
+    if (out_mem == RF_MEM_HOST) RF_HIP(sc.get(&d_out, out_bytes));  // (kept by the pool: no hipMalloc / hipFree pair -- and no device-wide sync -- per call)
     p.out = d_out;
     // Large ragged corpora: results in slot order into a temporary, then ONE gather into original order (rf_pack.hip
     // "gather_results_kernel" has the why: the scattered out[orig[slot]] stores of a length-bucketed corpus cost more than the scan).
@@ -1178,88 +1183,28 @@ rf_status run_many(const rf_comparator* c_in, const rf_corpus* corpus_in, rf_op 
         p.xcd_deal = tile_order >= 2 ? 1u : 0u;
     }
     static const size_t unscatter_min = [] { const char* e = getenv("RF_UNSCATTER_MIN"); return e ? (size_t)atoll(e) : (size_t)1 << 20; }();
-    void* d_tmp = nullptr;
-    bool tmp_owned = false;                 // d_tmp is this call's own stream-ordered allocation
-    StreamCache<rf_corpus::GatherTmp>::Lease kept;  // ... or this stream's kept buffer of the corpus; the lease is held while the scan + gather are enqueued
+    void* d_tmp = nullptr;  // this stream's kept buffer of the corpus, or a block of `sc` for the call
+    StreamCache<rf_corpus::GatherTmp>::Lease kept;  // (held while the scan + gather are enqueued)
+    const rf_corpus::GatherMaps* maps = nullptr;
     // (under a cutoff only the tiles of the passing length window write through orig[]; the gather is a fixed 10-12 bytes per
     // candidate of the WHOLE corpus, so it pays from a window of ~30 % of the tiles on: measured break-even, bench.py --ragged --cutoff)
     const bool wide_window = (uint64_t)(p.tile_end - p.tile_begin) * 10 >= (uint64_t)corpus->n_tiles * 3;
     const bool by_runs = !by_origin && scan_runs_applies(corpus, p, raw);  // small-cutoff scans of a bucketed corpus: one single-length view per length run
     if (want_slots || (unscatter_min && corpus->n >= unscatter_min && corpus->d_orig && !corpus->borrowed && corpus->n_slots && wide_window && !by_origin && !by_runs)) {
-        {
-            std::lock_guard<std::mutex> lock(corpus->scratch_mu);
-            if (!corpus->d_slot_ident) {
-                AccelTimer timer("slot maps + window table");
-                // once per corpus: the slot -> slot map the scans store through, and what the gather needs -- the window table
-                // (rf_pack.hip window_gather_kernel) when the slots are few enough ascending runs, else the candidate -> slot map
-                static const bool use_windows = [] { const char* e = getenv("RF_GATHER_WINDOWS"); return !e || atoi(e) != 0; }();
-                uint32_t *so = nullptr, *si = nullptr, *list = nullptr, *table = nullptr;
-                uint32_t n_runs = 0, n_rows = 0;
-                std::vector<uint32_t> runs(kMaxGatherRuns + 2, 0u);  // [0] = count, then the run starts
-                hipError_t e1 = hipMalloc((void**)&si, corpus->n_slots * sizeof(uint32_t));
-                if (e1 == hipSuccess && use_windows) {
-                    e1 = hipMalloc((void**)&list, runs.size() * sizeof(uint32_t));
-                    if (e1 == hipSuccess) e1 = hipMemsetAsync(list, 0, sizeof(uint32_t), st);
-                    if (e1 == hipSuccess) e1 = launch_run_starts(corpus->d_orig, (uint32_t)corpus->n_slots, list + 1, kMaxGatherRuns, list, st);
-                    if (e1 == hipSuccess) e1 = hipMemcpyAsync(runs.data(), list, (kMaxGatherRuns + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
-                    if (e1 == hipSuccess) e1 = hipStreamSynchronize(st);
-                    if (e1 == hipSuccess && runs[0] >= 1 && runs[0] <= kMaxGatherRuns) {
-                        n_runs = runs[0];
-                        std::sort(runs.begin() + 1, runs.begin() + 1 + n_runs);
-                        runs[1 + n_runs] = (uint32_t)corpus->n_slots;
-                        n_rows = (uint32_t)((corpus->n + kGatherWindow - 1) / kGatherWindow) + 1;
-                        e1 = hipMemcpyAsync(list, runs.data() + 1, (n_runs + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st);
-                        if (e1 == hipSuccess) e1 = hipMalloc((void**)&table, (size_t)n_rows * n_runs * sizeof(uint32_t));
-                        if (e1 == hipSuccess) e1 = launch_window_table(corpus->d_orig, list, n_runs, n_rows, table, st);
-                    }
-                }
-                if (e1 == hipSuccess && !table) {
-                    e1 = hipMalloc((void**)&so, corpus->n * sizeof(uint32_t));
-                    if (e1 == hipSuccess) e1 = hipMemsetAsync(so, 0xFF, corpus->n * sizeof(uint32_t), st);
-                }
-                if (e1 == hipSuccess) e1 = launch_slot_maps(corpus->d_orig, (uint32_t)corpus->n_slots, so, si, st);
-                // (round 5) the window gather reads a slot's place inside its span from 2 bytes instead of the 4 of orig[] (RF_GATHER_OFF16=0: the A/B switch;
-                // no room for them: the gather reads orig[] as before)
-                static const bool use_off16 = [] { const char* e = getenv("RF_GATHER_OFF16"); return !e || atoi(e) != 0; }();
-                uint16_t* o16 = nullptr;
-                if (e1 == hipSuccess && table && use_off16) {
-                    if (hipMalloc((void**)&o16, corpus->n_slots * sizeof(uint16_t)) != hipSuccess) (void)hipGetLastError(), o16 = nullptr;
-                    if (o16) e1 = launch_slot_off16(corpus->d_orig, (uint32_t)corpus->n_slots, o16, st);
-                }
-                if (e1 == hipSuccess) e1 = hipStreamSynchronize(st);  // (other streams may use the maps as soon as the lock is released)
-                if (list) (void)hipFree(list);
-                if (e1 != hipSuccess) {
-                    // Not an error: an HBM-tight caller keeps what round 2 gave it -- the launch below stores straight
-                    // through orig[] (scattered, slower, same values).  The next call tries again.
-                    if (so) (void)hipFree(so);
-                    if (si) (void)hipFree(si);
-                    if (table) (void)hipFree(table);
-                    if (o16) (void)hipFree(o16);
-                    (void)hipGetLastError();
-                } else {
-                    corpus->d_slot_of = so;
-                    corpus->d_window_table = table;
-                    corpus->d_slot_off16 = o16;
-                    corpus->gather_runs = n_runs;
-                    corpus->gather_rows = n_rows;
-                    corpus->d_slot_ident = si;
-                }
-            }
-        }
+        maps = corpus_gather_maps(corpus, st);
         if (want_slots) {
-            if (!corpus->d_slot_ident) {
-                if (out_mem == RF_MEM_HOST) scratch_free(d_out, st);
+            if (!maps) {
                 set_error("RF_FLAG_SLOT_ORDER: no device memory for the slot map");
                 return RF_ERR_OOM;
             }
             // the caller's vector IS the slot-ordered one: n_slots entries, no temporary, no gather
-            p.orig = corpus->d_slot_ident;
+            p.orig = maps->slot_ident.as<uint32_t>();
             p.slot_store = 1;
             p.mixed = nullptr;  // views, not scan_kernel_mixed: one slot per candidate
             p.mixed_end = 0;
             p.n = (uint32_t)corpus->n_slots;
             p.prefill_window = (args->flags & kFlagWindowInternal) ? 1u : 0u;
-        } else if (corpus->d_slot_ident) {
+        } else if (maps) {
         // the temporary: this stream's kept buffer (grown if this call needs f64 where u32 was kept); beyond 4 streams per corpus a
         // stream-ordered allocation for the call
         const size_t tmp_bytes = corpus->n_slots * elem;
@@ -1269,17 +1214,15 @@ rf_status run_many(const rf_comparator* c_in, const rf_corpus* corpus_in, rf_op 
             ea = kept->reserve(tmp_bytes);
             d_tmp = kept->ptr;
         } else if (ea == hipSuccess) {
-            ea = scratch_alloc(&d_tmp, tmp_bytes, st);
-            tmp_owned = true;
+            ea = sc.get(&d_tmp, tmp_bytes);
         }
         if (ea != hipSuccess) {  // no room for the temporary: scattered stores through orig[] as before (not an error)
             (void)hipGetLastError();
             d_tmp = nullptr;
-            tmp_owned = false;
             kept.release();
         } else {
             p.out = d_tmp;
-            p.orig = corpus->d_slot_ident;
+            p.orig = maps->slot_ident.as<uint32_t>();
             p.slot_store = 1;  // (d_slot_ident is kPad on padding lanes and the identity elsewhere; the temporary has n_slots entries)
             p.mixed = nullptr;  // views, not scan_kernel_mixed: one slot per candidate
             p.mixed_end = 0;
@@ -1287,14 +1230,7 @@ rf_status run_many(const rf_comparator* c_in, const rf_corpus* corpus_in, rf_op 
         }
         }
     }
-    if (const size_t scratch = launch_scratch_bytes(p, raw)) {
-        const hipError_t ea = scratch_alloc((void**)&p.long_scratch, scratch, st);
-        if (ea != hipSuccess) {
-            if (out_mem == RF_MEM_HOST) scratch_free(d_out, st);
-            if (d_tmp && tmp_owned) (void)scratch_free(d_tmp, st);  // (this call's own temporary must not outlive the failure)
-        }
-        RF_HIP(ea);
-    }
+    if (const size_t scratch = launch_scratch_bytes(p, raw)) RF_HIP(sc.get(&p.long_scratch, scratch));
     rf_corpus::TileLease tl;  // held while a filter pass and the scan over its list are enqueued
     // (... and the small-band scans of a single-length corpus: tiles with a few lanes left are listed for a dense second pass, rf_band.hip launch_band)
     const bool band_lists = p.band && raw == RAW_LEV && corpus->uniform && !p.tiles && !want_slots && p.tile_step == 1 && !by_runs;
@@ -1346,20 +1282,14 @@ rf_status run_many(const rf_comparator* c_in, const rf_corpus* corpus_in, rf_op 
                      d_tmp != nullptr, p.tile_begin, p.tile_end, corpus->n_tiles, p.prefill_none, p.data6 != nullptr);
     hipError_t e = by_runs ? launch_scan_runs(raw, p, c, corpus, op, f64_out, st) : (band_runs && band_runs_mode != 0 && p.band_defer_seen ? launch_band_runs(raw, p, corpus, st, band_runs_mode == 1) : launch_scan(raw, p, st, nullptr));
     tl.release();
-    if (p.long_scratch) (void)scratch_free(p.long_scratch, st);
     if (d_tmp) {
         if (e == hipSuccess)
-            e = corpus->d_window_table ? launch_window_gather(d_tmp, corpus->d_orig, corpus->d_slot_off16, corpus->d_window_table, corpus->gather_runs, corpus->gather_rows, d_out,
-                                                              (uint32_t)corpus->n, f64_out, st)
-                                       : launch_gather_results(d_tmp, corpus->d_slot_of, d_out, (uint32_t)corpus->n, f64_out, st);
-        if (tmp_owned) (void)scratch_free(d_tmp, st);
+            e = maps->window_table.ptr ? launch_window_gather(d_tmp, corpus->d_orig, maps->slot_off16.as<uint16_t>(), maps->window_table.as<uint32_t>(), maps->runs, maps->rows,
+                                                              d_out, (uint32_t)corpus->n, f64_out, st)
+                                       : launch_gather_results(d_tmp, maps->slot_of.as<uint32_t>(), d_out, (uint32_t)corpus->n, f64_out, st);
         kept.release();
     }
-    if (e == hipSuccess && out_mem == RF_MEM_HOST) {
-        e = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-    }
-    if (out_mem == RF_MEM_HOST) scratch_free(d_out, st);
+    if (e == hipSuccess && out_mem == RF_MEM_HOST) e = copy_home(out, d_out, out_bytes, st);
     if (e != hipSuccess) {
         set_error(std::string("scan launch: ") + hipGetErrorString(e));
         return e == hipErrorInvalidValue ? RF_ERR_UNSUPPORTED : RF_ERR_HIP;
@@ -1472,8 +1402,9 @@ static rf_status run_many_multi(const rf_comparator* const* cs_in, uint32_t q, c
         return RF_ERR_NO_DEVICE;
     }
     hipStream_t st = (hipStream_t)stream;
+    ScratchSet sc(st);
     char* d_out = static_cast<char*>(out);
-    if (out_mem == RF_MEM_HOST) RF_HIP(scratch_alloc((void**)&d_out, row_bytes * q, st));
+    if (out_mem == RF_MEM_HOST) RF_HIP(sc.get(&d_out, row_bytes * q));
 
     // fusable: single-word Levenshtein / LCS-family recurrences; the group key is what the kernel cannot vary per query
     // (a tight cutoff is better served by one early-out launch per query than by the fused kernel, which runs every column)
@@ -1519,14 +1450,8 @@ static rf_status run_many_multi(const rf_comparator* const* cs_in, uint32_t q, c
             e = launch_scan_multi(raws[i], p.len1 <= 32, p, st);
         }
     }
-    if (status == RF_OK && e == hipSuccess && out_mem == RF_MEM_HOST) {
-        e = hipMemcpyAsync(out, d_out, row_bytes * q, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-    }
-    if (out_mem == RF_MEM_HOST) {
-        if (status != RF_OK || e != hipSuccess) (void)hipStreamSynchronize(st);
-        scratch_free(d_out, st);
-    }
+    if (status == RF_OK && e == hipSuccess && out_mem == RF_MEM_HOST) e = copy_home(out, d_out, row_bytes * q, st);
+    if (out_mem == RF_MEM_HOST && (status != RF_OK || e != hipSuccess)) (void)hipStreamSynchronize(st);
     if (status != RF_OK) return status;
     if (e != hipSuccess) {
         set_error(std::string("multi-query scan: ") + hipGetErrorString(e));

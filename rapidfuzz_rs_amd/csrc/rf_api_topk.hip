@@ -14,7 +14,7 @@ static rf_status topk_core(const rf_comparator* c_in, const rf_corpus* corpus_in
 {
     const rf_args args_v = args ? sanitized_args(args, false) : rf_args{};  // (RF_FLAG_SLOT_ORDER is rf_many_*'s alone: the scores here are n-entry vectors)
     if (args) args = &args_v;
-    Effective eff;
+    Effective eff(st);
     if (const rf_status rs = make_effective(c_in, corpus_in, st, &eff); rs != RF_OK) return rs;
     const rf_comparator* c = eff.c;
     const rf_corpus* corpus = eff.corpus;
@@ -71,7 +71,8 @@ static rf_status topk_core(const rf_comparator* c_in, const rf_corpus* corpus_in
     p.key_index_base = key_index_base;
     // optionally also emit every candidate's score from the same pass (they stay sharded)
     uint32_t* d_all = out_all;
-    if (out_all && out_all_mem == RF_MEM_HOST) RF_HIP(scratch_alloc((void**)&d_all, corpus->n * sizeof(uint32_t), st));
+    ScratchSet temps(st);
+    if (out_all && out_all_mem == RF_MEM_HOST) RF_HIP(temps.get(&d_all, corpus->n * sizeof(uint32_t)));
     p.out = d_all;
     // Round 4: a top-k as the scan into a score vector + ONE pass over it (rf_select.hip topk_scores_kernel) -- for the shapes whose
     // plain scan is a whole-kernel asm scan WITHOUT a fast in-scan top-k form: Levenshtein over 2..4 words (queries of 65..256 symbols),
@@ -91,7 +92,6 @@ static rf_status topk_core(const rf_comparator* c_in, const rf_corpus* corpus_in
         const rf_status rs = run_many(c_in, corpus_in, op, args, d_scores, RF_MEM_DEVICE, st, false);
         hipError_t e = rs == RF_OK ? launch_topk_scores(p, d_scores, (uint32_t)corpus->n, st) : hipSuccess;
         if (rs == RF_OK && e == hipSuccess && out_all && out_all_mem == RF_MEM_HOST) e = hipMemcpyAsync(out_all, d_all, corpus->n * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
-        if (out_all && out_all_mem == RF_MEM_HOST) (void)scratch_free(d_all, st);
         if (rs != RF_OK) return rs;
         if (e != hipSuccess) {
             sc.discard();
@@ -124,7 +124,6 @@ static rf_status topk_core(const rf_comparator* c_in, const rf_corpus* corpus_in
     }
     if (e == hipSuccess) e = launch_scan(raw, p, st, nullptr);
     if (e == hipSuccess && out_all && out_all_mem == RF_MEM_HOST) e = hipMemcpyAsync(out_all, d_all, corpus->n * sizeof(uint32_t), hipMemcpyDeviceToHost, st);
-    if (out_all && out_all_mem == RF_MEM_HOST) (void)scratch_free(d_all, st);  // (on the failure paths too: ADVICE r4)
     if (e != hipSuccess) {
         sc.discard();  // (the scratch may be left half-armed)
         set_error(std::string("top-k: ") + hipGetErrorString(e));
@@ -141,14 +140,10 @@ static rf_status select_topk(const void* d_scores, bool f64, bool desc, uint32_t
     keys->clear();
     idx->clear();
     const uint32_t nb = select_blocks(n);
+    ScratchSet sc(st);
     uint8_t* mem = nullptr;
     const size_t hist_bytes = 2048 * sizeof(unsigned long long), cnt_bytes = (size_t)nb * sizeof(uint32_t);
-    RF_HIP(scratch_alloc((void**)&mem, 64 + hist_bytes + 2 * cnt_bytes, st));
-    struct Free {
-        uint8_t* p;
-        hipStream_t st;
-        ~Free() { (void)scratch_free(p, st); }
-    } free_mem{mem, st};
+    RF_HIP(sc.get(&mem, 64 + hist_bytes + 2 * cnt_bytes));
     unsigned long long* d_hist = reinterpret_cast<unsigned long long*>(mem + 64);
     uint32_t* d_less = reinterpret_cast<uint32_t*>(mem + 64 + hist_bytes);
     uint32_t* d_eq = d_less + nb;
@@ -204,8 +199,7 @@ static rf_status select_topk(const void* d_scores, bool f64, bool desc, uint32_t
     const uint32_t need_eq = (uint32_t)(kk - n_less);
     uint8_t* out = nullptr;
     const size_t key_bytes = f64 ? 8 : 4;
-    RF_HIP(scratch_alloc((void**)&out, kk * (key_bytes + 4), st));
-    Free free_out{out, st};
+    RF_HIP(sc.get(&out, kk * (key_bytes + 4)));
     uint32_t* d_idx = reinterpret_cast<uint32_t*>(out + kk * key_bytes);
     RF_HIP(launch_select_count(d_scores, f64, n, desc, T, d_less, d_eq, st));
     RF_HIP(launch_select_emit(d_scores, f64, n, desc, T, d_less, d_eq, (uint32_t)n_less, need_eq, out, d_idx, st));
@@ -234,16 +228,11 @@ static rf_status topk_by_selection(const rf_comparator* c, const rf_corpus* corp
     const size_t elem = f64 ? sizeof(double) : sizeof(uint32_t);
     *desc = op == RF_OP_SIMILARITY || op == RF_OP_NORMALIZED_SIMILARITY;
     void* d_scores = out_all;
-    const bool temp = !(out_all && out_all_mem == RF_MEM_DEVICE);
-    if (temp) RF_HIP(scratch_alloc(&d_scores, corpus->n * elem, st));
+    ScratchSet sc(st);
+    if (!(out_all && out_all_mem == RF_MEM_DEVICE)) RF_HIP(sc.get(&d_scores, corpus->n * elem));
     rf_status s = run_many(c, corpus, op, args, d_scores, RF_MEM_DEVICE, st, f64);
     if (s == RF_OK) s = select_topk(d_scores, f64, *desc, (uint32_t)corpus->n, k, st, keys, idx);
-    if (s == RF_OK && out_all && out_all_mem == RF_MEM_HOST) {
-        hipError_t e = hipMemcpyAsync(out_all, d_scores, corpus->n * elem, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) s = RF_ERR_HIP;
-    }
-    if (temp) (void)scratch_free(d_scores, st);
+    if (s == RF_OK && out_all && out_all_mem == RF_MEM_HOST && copy_home(out_all, d_scores, corpus->n * elem, st) != hipSuccess) s = RF_ERR_HIP;
     return s;
 }
 
@@ -320,8 +309,9 @@ try {
         return RF_ERR_NO_DEVICE;
     }
     hipStream_t st = (hipStream_t)stream;
+    ScratchSet sc(st);
     uint64_t* d_best = nullptr;
-    RF_HIP(scratch_alloc((void**)&d_best, (size_t)kWave * sizeof(uint64_t), st));
+    RF_HIP(sc.get(&d_best, (size_t)kWave * sizeof(uint64_t)));
     bool desc = false;
     std::vector<uint64_t> best(kWave, ~0ull);
     hipError_t e = hipSuccess;
@@ -356,7 +346,7 @@ try {
         e = hipSuccess;
         if (s == RF_OK) e = hipMemcpyAsync(best.data(), d_best, k * sizeof(uint64_t), hipMemcpyDeviceToHost, st);
     }
-    (void)scratch_free(d_best, st);
+    sc.reset();  // (before the selection path below allocates its own)
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (s == RF_ERR_UNSUPPORTED && (op == RF_OP_DISTANCE || op == RF_OP_SIMILARITY)) {
         // shapes the in-scan lists do not cover (queries beyond 512 symbols, general weight tables): score everything, select
@@ -513,17 +503,16 @@ try {
     const bool f64 = !usize_metric || op == RF_OP_NORMALIZED_DISTANCE || op == RF_OP_NORMALIZED_SIMILARITY;
     if (!f64 && k <= (uint64_t)kWave) {
         // the in-scan lists: keys with the LOCAL index, widened on the device -- nothing synchronizes
+        ScratchSet sc(st);  // (released before the selection path below allocates its own)
         uint64_t* d_keys = nullptr;
-        RF_HIP(scratch_alloc((void**)&d_keys, (size_t)kWave * sizeof(uint64_t), st));
+        RF_HIP(sc.get(&d_keys, (size_t)kWave * sizeof(uint64_t)));
         bool desc = false;
         const rf_status s = topk_core(c, corpus, op, args, (uint32_t)k, 0, d_keys, nullptr, RF_MEM_HOST, st, &desc);
         if (s == RF_OK) {
             const hipError_t e = launch_keys_to_entries(d_keys, (uint32_t)k, index_base, d_entries_out, st);
-            (void)scratch_free(d_keys, st);
             RF_HIP(e);
             return RF_OK;
         }
-        (void)scratch_free(d_keys, st);
         if (s != RF_ERR_UNSUPPORTED) return s;  // (long queries, general weight tables: the selection path below)
     }
     std::vector<uint64_t> keys;

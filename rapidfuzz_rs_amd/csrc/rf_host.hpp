@@ -168,10 +168,19 @@ public:
 struct DeviceBuf : NoCopy {
     void* ptr = nullptr;
     size_t cap = 0;  // bytes
+    DeviceBuf() = default;
+    DeviceBuf(DeviceBuf&& o) noexcept : ptr(std::exchange(o.ptr, nullptr)), cap(std::exchange(o.cap, 0)) {}
+    DeviceBuf& operator=(DeviceBuf&& o) noexcept  // (what was held here goes to `o`, which frees it)
+    {
+        std::swap(ptr, o.ptr), std::swap(cap, o.cap);
+        return *this;
+    }
     ~DeviceBuf()
     {
         if (ptr) (void)hipFree(ptr);
     }
+    template <class T>
+    T* as() const { return static_cast<T*>(ptr); }
     hipError_t reserve(size_t bytes)
     {
         if (cap >= bytes) return hipSuccess;
@@ -218,19 +227,6 @@ struct rf_corpus {
     TileDesc* d_tiles_by_origin = nullptr;  // the same descriptors with the non-empty exact tiles ordered by their first candidate's original index (tiles_by_origin())
     uint32_t* d_orig = nullptr;  // nullptr = identity (single length bucket, original order)
     size_t n_slots = 0;          // entries of d_orig: 64 per tile (exact tiles, then the views)
-    // large ragged corpora return their results through a slot-ordered temporary + one gather (rf_pack.hip): built on first use
-    mutable uint8_t* d_heads8 = nullptr;       // head plane: the first 8 symbols of every candidate (small-cutoff scans; built on first use)
-    mutable uint32_t* d_heads6 = nullptr;      // the same at 6 bits per symbol (single-length corpora of < 64 distinct symbols; ScanParams::heads6)
-    mutable bool heads6_tried = false;
-    mutable uint32_t* d_data6 = nullptr;       // the payload at 6 bits per symbol (single-length corpora of < 64 distinct symbols; ScanParams::data6); built on first use
-    mutable bool data6_tried = false;
-    mutable uint32_t max_stored_sym = 0xFFFFFFFFu;  // largest stored symbol of the payload, exact; 0xFFFFFFFF = not computed yet (corpus_max_stored_symbol)
-    mutable uint32_t* d_slot_of = nullptr;     // candidate -> its slot
-    mutable uint32_t* d_slot_ident = nullptr;  // slot -> slot, kPad on padding lanes (stands in for d_orig in such a launch)
-    mutable uint32_t* d_len_of = nullptr;      // candidate -> its length (original order): the normalizing pass of run_many's two-step path; built on first use
-    mutable uint16_t* d_slot_off16 = nullptr;  // slot -> original index mod kGatherOff16Mod (0xFFFF: padding): what the window gather reads instead of d_orig
-    mutable uint32_t* d_window_table = nullptr;  // the coalesced gather's table (rf_pack.hip window_table_kernel): gather_rows x gather_runs
-    mutable uint32_t gather_runs = 0, gather_rows = 0;
     uint32_t n_tiles = 0;        // exact tiles, then the virtual (one-length) views of the mixed section
     uint32_t n_exact = 0;        // tiles [0, n_exact) are exact-length tiles; [n_exact, n_tiles) virtual views (HostLayout)
     bool exact_dense = false;    // no padding lane in tiles [0, n_exact) (false under RF_NO_MIXED_TILES when a length's count is not a multiple of 64: its last tile is partial)
@@ -248,7 +244,28 @@ struct rf_corpus {
     uint8_t sigma[256];           // symbol renaming: the packed corpus stores sigma[c] for candidate byte c
     float sym_freq[256] = {0};    // relative frequency of candidate byte c (from the histogram sigma is made of; all zero = unknown)
     uint8_t* d_sigma = nullptr;   // device copy
-    mutable std::mutex scratch_mu;  // guards the structures a call builds on first use (the mutable members here, the caches below aside)
+    // The structures a call builds on first use (rf_api_scan.hip corpus_*), guarded by scratch_mu.  Each builder fills a local owner,
+    // synchronizes its stream and only then publishes it here by move, under the lock: other streams see complete structures or none.
+    struct GatherMaps {  // large ragged corpora return their results through a slot-ordered temporary + one gather (rf_pack.hip); published together
+        DeviceBuf slot_ident;    // slot -> slot, kPad on padding lanes (stands in for d_orig in such a launch)
+        DeviceBuf slot_of;       // candidate -> its slot (when there is no window table)
+        DeviceBuf window_table;  // the coalesced gather's table (rf_pack.hip window_table_kernel): rows x runs
+        DeviceBuf slot_off16;    // slot -> original index mod kGatherOff16Mod (0xFFFF: padding): what the window gather reads instead of d_orig (optional)
+        uint32_t runs = 0, rows = 0;
+        uint64_t bytes() const { return slot_ident.bytes() + slot_of.bytes() + window_table.bytes() + slot_off16.bytes(); }
+    };
+    struct Accel : NoCopy {
+        DeviceBuf heads8;  // head plane: the first 8 symbols of every candidate (small-cutoff scans)
+        DeviceBuf heads6;  // the same at 6 bits per symbol (single-length corpora of < 64 distinct symbols; ScanParams::heads6); tried once
+        DeviceBuf data6;   // the payload at 6 bits per symbol (the same corpora; ScanParams::data6); tried once
+        DeviceBuf len_of;  // candidate -> its length (original order): the normalizing pass of run_many's two-step path
+        GatherMaps gather;
+        bool heads6_tried = false, data6_tried = false;
+        uint32_t max_stored_sym = 0xFFFFFFFFu;  // largest stored symbol of the payload, exact; 0xFFFFFFFF = not computed yet (corpus_max_stored_symbol)
+        uint64_t bytes() const { return heads8.bytes() + heads6.bytes() + data6.bytes() + len_of.bytes() + gather.bytes(); }
+    };
+    mutable Accel accel;
+    mutable std::mutex scratch_mu;  // guards `accel` and d_sigma_identity (the caches below have their own)
     // Per-stream buffers (StreamCache), at most 8 top-k scratches, 4 gather temporaries and 4 tile lists.  The top-k scratch: [64 way
     // segments of candidate keys | root table 64 x 64 keys | bound (u64, own line) | control block 65 x 128 B], room for every workgroup
     // of the largest grid any top-k launch uses to publish a full 64-entry list.  The kernels leave bound / counters re-armed, so a
@@ -361,6 +378,43 @@ inline rf_args sanitized_args(const rf_args* a, bool slots_allowed)
 }
 __attribute__((visibility("hidden"))) extern std::atomic<uint64_t> g_corpus_uid;
 
+// the library's stream-ordered scratch allocator (rf_scratch.hip: why it is not hipMallocAsync).  scratch_free parks the block behind
+// everything enqueued on `st` so far; neither call ever waits.  Calls hold their blocks in a ScratchSet.
+extern "C" {
+__attribute__((visibility("hidden"))) hipError_t scratch_alloc(void** out, size_t bytes, hipStream_t st);
+__attribute__((visibility("hidden"))) void scratch_free(void* p, hipStream_t st);
+__attribute__((visibility("hidden"))) void scratch_trim(void);
+}
+// Everything one call takes from scratch_alloc, bound to the call's stream.  The destructor hands every block back with scratch_free -- on
+// every way out of the call, error returns included; reset() does it early, where a later allocation of the same call may reuse them.
+class ScratchSet : NoCopy {
+    hipStream_t st_;
+    std::vector<void*> blocks_;
+
+public:
+    explicit ScratchSet(hipStream_t st) : st_(st) {}
+    ScratchSet(ScratchSet&& o) noexcept : st_(o.st_), blocks_(std::exchange(o.blocks_, {})) {}
+    ~ScratchSet() { reset(); }
+    template <class T>
+    hipError_t get(T** p, size_t bytes)
+    {
+        const hipError_t e = scratch_alloc(reinterpret_cast<void**>(p), bytes, st_);
+        if (e == hipSuccess) blocks_.push_back((void*)*p);
+        return e;
+    }
+    void reset()
+    {
+        for (void* b : blocks_) scratch_free(b, st_);
+        blocks_.clear();
+    }
+};
+// an RF_MEM_HOST result: its device staging copied home, and waited for
+inline hipError_t copy_home(void* host, const void* dev, size_t bytes, hipStream_t st)
+{
+    const hipError_t e = hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st);
+    return e == hipSuccess ? hipStreamSynchronize(st) : e;
+}
+
 // Symbol renaming.  Every column of every kernel gathers 64 table rows from LDS, one per lane, and LDS bank
 // conflicts between DIFFERENT symbols that share a bank (row index mod 32 for 8-byte rows) are the cost of that
 // gather -- ASCII classes collide systematically ('A'/'a', digits/'P'..'Y').  Renaming symbols by frequency rank
@@ -372,20 +426,15 @@ using ComparatorRef = std::shared_ptr<rf_comparator>;
 // per-call byte image of the corpus translated from its raw symbol stream (translate_kernel: query symbol -> its id,
 // anything else -> 0).  The image is a borrowed view (same tiles / slot map) that lives until the object goes out of
 // scope; its payload is released in stream order.
-extern "C" __attribute__((visibility("hidden"))) void scratch_free(void* p, hipStream_t st);  // rf_scratch.hip
 struct Effective {
+    explicit Effective(hipStream_t st) : scratch(st) {}
     const rf_comparator* c = nullptr;
     ComparatorRef hold;  // keeps a lowered comparator alive for the duration of the call
     const rf_corpus* corpus = nullptr;
     std::unique_ptr<rf_corpus> image;
-    uint8_t* temp = nullptr;
-    hipStream_t stream = nullptr;
+    ScratchSet scratch;  // the image's payload
     std::vector<uint32_t> keys;
     std::vector<uint8_t> vals;
-    ~Effective()
-    {
-        if (temp) scratch_free(temp, stream);
-    }
 };
 constexpr size_t kTailPad = (size_t)kWave * kChunk;  // one readable chunk row past the last tile
 static inline uint64_t tile_bytes(uint32_t len) { return (uint64_t)((len + kChunk - 1) / kChunk) * kWave * kChunk; }
@@ -417,11 +466,6 @@ static inline uint64_t tile_bytes(uint32_t len) { return (uint64_t)((len + kChun
 // (hidden: these are internal to librfgpu.so -- only the rf_* entry points of include/rfgpu.h are exported)
 #define RF_LOCAL __attribute__((visibility("hidden")))
 extern "C" {
-// the library's stream-ordered scratch allocator (rf_scratch.hip: why it is not hipMallocAsync).  scratch_free parks the block behind
-// everything enqueued on `st` so far; neither call ever waits.
-RF_LOCAL hipError_t scratch_alloc(void** out, size_t bytes, hipStream_t st);
-RF_LOCAL void scratch_free(void* p, hipStream_t st);
-RF_LOCAL void scratch_trim(void);
 RF_LOCAL void symbol_frequencies(const uint64_t* hist, float* freq);                                                      // rf_api.hip
 RF_LOCAL rf_status resolve(const rf_comparator* c, const rf_corpus* corpus, const rf_comparator** eff, ComparatorRef* hold, bool* overflow_hit = nullptr);  // rf_api.hip
 RF_LOCAL rf_status make_effective(const rf_comparator* c_in, const rf_corpus* corpus, hipStream_t st, Effective* e);     // rf_api.hip
