@@ -22,7 +22,7 @@
  * Environment variables.  The library reads the following variables ONCE per process (first use).  Every one of them selects
  * between kernels / layouts / launch shapes that return IDENTICAL results -- they exist for A/B measurements and for the
  * forced-path test runs (tests/multitile_check.py) -- and none is needed in production; the default is what ships.
- * There is no variable that changes a result: the measurement switch that does (RF_EXP_NOHBM) is compiled only into
+ * There is no variable that changes a result: the measurement switches that do (RF_EXP_NOHBM, RF_EXP_TILE_BYTES) are compiled only into
  * -DRF_EXPERIMENTS builds (tools/build_stream_variant.sh), never into librfgpu.so (tests/test_abi.py checks the binary).
  *   name                          default   meaning
  *   RF_SCAN_BLOCKS_PER_CU         32        workgroups per CU of short-running launches (cutoff scans, band kernel, long queries)

@@ -30,7 +30,7 @@ void symbol_frequencies(const uint64_t* hist, float* freq)
 }
 static void make_sigma(const uint64_t* hist, uint8_t* sigma)
 {
-    static const bool disabled = getenv("RF_NO_RENAME") != nullptr;  // tuning / A-B knob
+    static const bool disabled = env_set("RF_NO_RENAME");  // tuning / A-B knob
     int order[256];
     for (int i = 0; i < 256; ++i) order[i] = i;
     if (!disabled)
@@ -420,7 +420,7 @@ struct HostLayout {
 };
 
 struct PhaseTimer {  // RF_PACK_TIMING=1 prints where rf_corpus_pack spends its time
-    bool on = getenv("RF_PACK_TIMING") != nullptr;
+    bool on = sw_pack_timing();
     std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
     void lap(const char* what)
     {
@@ -466,7 +466,7 @@ static rf_status build_layout(const uint8_t* bytes, const uint64_t* offsets, siz
     // a single length bucket in original order is addressed arithmetically (tile t at t * tile_bytes), last tile partial
     L->identity = groups.size() <= 1 && tile_bytes(max_len) <= 0xFFFFFFFFull;
     L->max_len = max_len;
-    static const bool no_mixed = getenv("RF_NO_MIXED_TILES") != nullptr;  // A/B switch: round-1 layout (every length padded to whole tiles)
+    const bool no_mixed = sw_no_mixed_tiles();  // A/B switch: round-1 layout (every length padded to whole tiles)
 
     // 2. exact tiles: whole multiples of 64 per length, ascending (everything, for the identity layout)
     uint64_t slots = 0, data_bytes = 0, pool_n = 0;
@@ -842,7 +842,7 @@ struct DeviceTemps {  // released on every way out
 static rf_status pack_ragged_device(const uint8_t* bytes, const uint64_t* offsets, size_t n, int device, rf_corpus** out, bool* declined)
 {
     *declined = true;
-    static const size_t min_n = [] { const char* e = getenv("RF_DEVICE_PACK_MIN"); return e ? (size_t)atoll(e) : (size_t)1 << 16; }();  // 0: never
+    static const size_t min_n = (size_t)env_int("RF_DEVICE_PACK_MIN", 65536);  // 0: never
     constexpr uint32_t kMaxLen = 0xFFFFu;
     if (!min_n || n < min_n || n >= 0x7FFFFFFFull || !offsets) return RF_OK;
     const uint64_t first = offsets[0], total = offsets[n];
@@ -911,7 +911,7 @@ static rf_status pack_ragged_device(const uint8_t* bytes, const uint64_t* offset
             }
     }
     const bool identity = groups.size() <= 1 && tile_bytes(max_len) <= 0xFFFFFFFFull;
-    static const bool no_mixed = getenv("RF_NO_MIXED_TILES") != nullptr;
+    const bool no_mixed = sw_no_mixed_tiles();
     std::vector<TileDesc> tiles;
     bool exact_dense = true;
     uint64_t slots = 0, data_bytes = 0, pool_n = 0;

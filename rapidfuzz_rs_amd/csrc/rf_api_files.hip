@@ -48,7 +48,7 @@ bool read_parallel(int fd, uint64_t off, uint8_t* dst, size_t n)
 {
     // (RF_STREAM_THREADS: reader threads of the streamed scans and of rf_corpus_load; default 16 -- the page-cache -> pinned-buffer copy
     // runs at ~5 GB/s per thread, and it is this copy, not the link, that bounds a streamed scan: profiles/stream_r04.txt)
-    static const size_t max_threads = [] { const char* e = getenv("RF_STREAM_THREADS"); const int v = e ? atoi(e) : 16; return (size_t)(v > 0 ? v : 1); }();
+    static const size_t max_threads = (size_t)std::max(1ll, env_int("RF_STREAM_THREADS", 16));
     const size_t nthreads = n < (32u << 20) ? 1 : std::min<size_t>(max_threads, std::max<size_t>(1, std::thread::hardware_concurrency()));
     std::atomic<bool> ok{true};
     auto worker = [&](size_t t) {
@@ -527,7 +527,7 @@ static rf_status stream_many(const rf_comparator* c, const char* path, rf_op op,
     // costs 50-80 ms, a third of a 6.4 GB streamed scan (profiles/stream_r04.txt).  One streamed scan at a time uses the kept sets (a
     // concurrent one allocates its own); a call that needs larger segments replaces them.  RF_STREAM_KEEP=0: allocate and free per call.
     KeptSets& kept = kept_sets();
-    static const bool keep_sets = [] { const char* e = getenv("RF_STREAM_KEEP"); return !e || atoi(e) != 0; }();
+    static const bool keep_sets = env_on("RF_STREAM_KEEP");
     std::unique_lock<std::mutex> kept_lock(kept.mu, std::defer_lock);
     const bool use_kept = keep_sets && kept_lock.try_lock();
     if (use_kept && (kept.cap < max_seg + kTailPad || kept.device != device)) {
@@ -609,7 +609,7 @@ static rf_status stream_many(const rf_comparator* c, const char* path, rf_op op,
             }
         });
     std::vector<TileDesc> seg_tiles;
-    static const bool stream_timing = getenv("RF_STREAM_TIMING") != nullptr;  // phase times of a streamed scan on stderr
+    const bool stream_timing = sw_stream_timing();  // phase times of a streamed scan on stderr
     using clk = std::chrono::steady_clock;
     if (stream_timing) std::fprintf(stderr, "[rf stream] set-up (streams, device + pinned buffers, None pre-fill) %.1f ms\n", std::chrono::duration<double, std::milli>(t_loop - t_enter).count());
     for (size_t k = 0; ok && status == RF_OK && k + 1 < cuts.size(); ++k) {
@@ -704,7 +704,7 @@ static rf_status stream_many(const rf_comparator* c, const char* path, rf_op op,
         pending = std::current_exception();
     }
     using clk = std::chrono::steady_clock;
-    static const bool stream_timing = getenv("RF_STREAM_TIMING") != nullptr;  // phase times of a streamed scan on stderr
+    const bool stream_timing = sw_stream_timing();  // phase times of a streamed scan on stderr
     const auto t_tail = clk::now();
     if (res_thread.joinable()) {
         {

@@ -82,8 +82,7 @@ static rf_status filter_fast(const rf_comparator* c_in, const rf_corpus* corpus_
                              ScratchSet& sc, bool* took, void** lane_val, uint32_t** lane_idx, uint32_t** d_total, uint32_t* cap2_out, rf_corpus::TileLease* held)
 {
     *took = false;
-    static const bool lane_compact = [] { const char* e = getenv("RF_LANE_COMPACT"); return !e || atoi(e) != 0; }();
-    if (!lane_compact || !corpus_in->uniform || corpus_in->borrowed || corpus_in->wide || c_in->wide) return RF_OK;
+    if (!corpus_in->uniform || corpus_in->borrowed || corpus_in->wide || c_in->wide) return RF_OK;
     const rf_comparator* c = c_in;
     const rf_corpus* corpus = corpus_in;
     ScanParams p;
@@ -96,9 +95,9 @@ static rf_status filter_fast(const rf_comparator* c_in, const rf_corpus* corpus_
     p.heads6 = corpus_head6_plane(corpus, st);
     plan_band_filter(c, corpus, op, f64_out, &p, corpus->uniform_len);
     rf_corpus::TileLease list = corpus->tile_list_lease(st);
-    p.tile_list_buf = list ? list->ptr : nullptr;
+    if (list) list->lend(p);
     p.lane_list = list ? 1u : 0u;
-    if (!p.lane_list || !head_two_pass_applies(raw, p)) return RF_OK;
+    if (early_road(raw, p) != EarlyRoad::TwoPassLanes) return RF_OK;
     // room for the survivors of the first pass (NOT the passers: a corpus that shares prefixes with the query has many more survivors than matches); a call whose
     // survivors do not fit takes the second road afterwards -- correct either way
     const uint64_t want = std::max<uint64_t>(std::max<uint64_t>(corpus->n / 4, 4 * capacity), 1u << 16);
@@ -108,12 +107,12 @@ static rf_status filter_fast(const rf_comparator* c_in, const rf_corpus* corpus_
     *lane_idx = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(*lane_val) + (size_t)cap2 * elem);
     p.lane_val = *lane_val;
     p.lane_idx = *lane_idx;
-    *d_total = p.tile_list_buf + 1;  // (the survivors' number, left there by the pack kernel; `held` keeps other host threads of this stream off the buffer until
+    *d_total = p.tile_list_buf + ListLayout::kLaneSurvivorsAt;  // (the survivors' number, left there by the pack kernel; `held` keeps other host threads of this stream off the buffer until
                                      // everything that reads it has been enqueued)
     p.lane_cap = cap2;
     p.out = nullptr;
     p.prefill_none = 0;
-    static const bool trace_plan = getenv("RF_TRACE_PLAN") != nullptr;
+    const bool trace_plan = sw_trace_plan();
     if (trace_plan) std::fprintf(stderr, "[rf plan] filter: lane compaction, first_check=%u head_need=%u head_k=%u room for %u survivors\n", p.first_check, p.head_need, p.head_k, cap2);
     const hipError_t e = launch_scan(raw, p, st, nullptr);
     *held = std::move(list);

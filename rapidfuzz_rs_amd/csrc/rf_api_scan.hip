@@ -250,7 +250,7 @@ rf_status plan(const rf_comparator* c, const rf_corpus* corpus, rf_op op, const 
     // Long query + small distance cutoff (the reference's hyrroe2003_small_band_with_pm, levenshtein.rs:509-617, taken when
     // len1 > 64 and 2k + 1 <= 64, :1059-1062): one 64-bit word sliding down the diagonal instead of ceil(len1 / 64) words
     // per column.  k is the cutoff on the RAW distance (the common weight factor divided out).
-    static const bool no_band = getenv("RF_NO_BAND") != nullptr;  // A/B switch
+    static const bool no_band = env_set("RF_NO_BAND");  // A/B switch
     if (!no_band && *raw == RAW_LEV && p->finish == FIN_LEV && p->factor >= 1 && op == RF_OP_DISTANCE && !f64_out && p->has_cutoff && c->words >= 2 &&
         c->words <= 64 && p->cutoff_u32 / p->factor <= 31) {
         p->band = 1;
@@ -293,7 +293,7 @@ rf_status plan(const rf_comparator* c, const rf_corpus* corpus, rf_op op, const 
             p->early = 1;
             // where a tile's first chunk takes its first look (scan_body): unrelated strings gain almost one edit per column
             {
-                static const int forced = [] { const char* e = getenv("RF_FIRST_CHECK"); return e ? atoi(e) : 0; }();  // A/B switch
+                static const int forced = (int)env_int("RF_FIRST_CHECK", 0);  // A/B switch
                 const double raw_allowed = slack * maximum / (double)std::max<uint32_t>(1u, (uint32_t)std::abs(p->fin_dR));
                 // measured on the C2 corpus (cutoffs 0..12, looks at 4..16): the best look is the first even column >= cutoff + 3
                 // (cutoff 3: 195 -> 213 Gpairs/s, cutoff 0: 197 -> 233, cutoff 8: 125 -> 159)
@@ -372,7 +372,7 @@ static size_t launch_scratch_bytes(const ScanParams& p, RawKind raw)
 // RF_PACK_TIMING=1: what the structures a corpus builds on first use cost (stderr, one line each) -- bench.py's accel_build_ms, itemised
 struct AccelTimer {
     const char* what;
-    bool on = getenv("RF_PACK_TIMING") != nullptr;
+    bool on = sw_pack_timing();
     std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
     explicit AccelTimer(const char* w) : what(w) {}
     ~AccelTimer()
@@ -418,7 +418,7 @@ static uint32_t corpus_max_stored_symbol(const rf_corpus* corpus, hipStream_t st
 // Failing to allocate it is not an error: the scan then reads the tiles' first chunk rows as before (the next call tries again).
 const uint8_t* corpus_head8_plane(const rf_corpus* corpus, const ScanParams& p, RawKind raw, hipStream_t st)
 {
-    static const size_t min_tiles = [] { const char* e = getenv("RF_HEAD8_MIN"); return e ? (size_t)atoll(e) : (size_t)1 << 14; }();
+    static const size_t min_tiles = (size_t)env_int("RF_HEAD8_MIN", 16384);
     if (!min_tiles || !p.early || (raw != RAW_LEV && raw != RAW_OSA) || p.words != 1 || p.first_check > 8 || corpus->borrowed)
         return nullptr;
     // single-length corpora: every tile; length-bucketed corpora (round 4): the exact tiles, whose length runs the cutoff scans
@@ -444,7 +444,7 @@ const uint8_t* corpus_head8_plane(const rf_corpus* corpus, const ScanParams& p, 
 // (+ 6 bytes per candidate); RF_HEAD6=0 switches it off.  nullptr = not to be had (tried once).
 const uint32_t* corpus_head6_plane(const rf_corpus* corpus, hipStream_t st)
 {
-    static const bool on = [] { const char* e = getenv("RF_HEAD6"); return !e || atoi(e) != 0; }();
+    static const bool on = env_on("RF_HEAD6");
     if (!on || !corpus->uniform || !corpus->accel.heads8.ptr || corpus->borrowed) return nullptr;
     if (corpus_max_stored_symbol(corpus, st) >= 64u) return nullptr;
     std::lock_guard<std::mutex> lock(corpus->scratch_mu);
@@ -466,8 +466,8 @@ const uint32_t* corpus_head6_plane(const rf_corpus* corpus, hipStream_t st)
 // from the 8-bit payload on first use by a scan that streams it (tried once), kept beside it (+ 75 % of the payload in HBM); RF_PACK6=0 switches it off.
 const uint32_t* corpus_data6(const rf_corpus* corpus, hipStream_t st)
 {
-    static const bool on = [] { const char* e = getenv("RF_PACK6"); return !e || atoi(e) != 0; }();
-    static const uint32_t min_tiles = [] { const char* e = getenv("RF_PACK6_MIN_TILES"); return e ? (uint32_t)atoll(e) : 16384u; }();
+    static const bool on = env_on("RF_PACK6");
+    static const uint32_t min_tiles = (uint32_t)env_int("RF_PACK6_MIN_TILES", 16384);
     if (!on || corpus->borrowed || corpus->n_tiles < min_tiles) return nullptr;
     if (corpus->uniform ? corpus->uniform_len == 0 : (!corpus->d_tiles || corpus->data_bytes % (kWave * kChunk) != 0)) return nullptr;
     // (whole chunks: any 64 codes; the partial last chunk of a single-length corpus is filled up with the code 63, which must then be free; bucketed corpora: the
@@ -512,10 +512,10 @@ static const uint32_t* corpus_len_of(const rf_corpus* corpus, hipStream_t st)
 // the launch stores straight through orig[] (scattered, slower, same values).  The next call tries again.
 static const rf_corpus::GatherMaps* corpus_gather_maps(const rf_corpus* corpus, hipStream_t st)
 {
-    static const bool use_windows = [] { const char* e = getenv("RF_GATHER_WINDOWS"); return !e || atoi(e) != 0; }();
+    static const bool use_windows = env_on("RF_GATHER_WINDOWS");
     // (round 5) the window gather reads a slot's place inside its span from 2 bytes instead of the 4 of orig[] (RF_GATHER_OFF16=0: the A/B switch;
     // no room for them: the gather reads orig[] as before)
-    static const bool use_off16 = [] { const char* e = getenv("RF_GATHER_OFF16"); return !e || atoi(e) != 0; }();
+    static const bool use_off16 = env_on("RF_GATHER_OFF16");
     std::lock_guard<std::mutex> lock(corpus->scratch_mu);
     rf_corpus::GatherMaps& maps = corpus->accel.gather;
     const uint32_t n_slots = (uint32_t)corpus->n_slots;
@@ -565,7 +565,7 @@ void plan_band_filter(const rf_comparator* c, const rf_corpus* corpus, rf_op op,
 {
     p->head_need = 0;
     if (!p->heads8 || !p->early || p->words != 1 || len2 < 8) return;
-    static const int forced = [] { const char* e = getenv("RF_BAND_FILTER"); return e ? atoi(e) : -1; }();
+    static const int forced = (int)env_int("RF_BAND_FILTER", -1);
     if (forced == 0) return;
     const uint32_t len1 = p->len1;
     const uint32_t Sv = len1 + len2, Mv = std::max(len1, len2);
@@ -616,7 +616,7 @@ void plan_band_filter(const rf_comparator* c, const rf_corpus* corpus, rf_op op,
 // kernels that lose by it
 static int tile_order_knob()
 {
-    static const int v = [] { const char* e = getenv("RF_TILE_ORDER"); return e ? atoi(e) : 2; }();
+    static const int v = (int)env_int("RF_TILE_ORDER", 2);
     return v;
 }
 
@@ -635,7 +635,7 @@ static bool scan_runs_applies(const rf_corpus* corpus, const ScanParams& p, RawK
 }
 static hipError_t launch_scan_runs(RawKind raw, const ScanParams& p, const rf_comparator* c, const rf_corpus* corpus, rf_op op, bool f64_out, hipStream_t st)
 {
-    static const uint32_t min_run = [] { const char* e = getenv("RF_RUN_MIN_TILES"); return e ? (uint32_t)atoi(e) : 256u; }();
+    static const uint32_t min_run = (uint32_t)env_int("RF_RUN_MIN_TILES", 256);
     hipError_t e = hipSuccess;
     if (p.out && !p.topk_k) {
         const size_t w = p.out_f64 ? 2 : 1, from = p.prefill_window ? (size_t)p.tile_begin * kWave : 0, count = p.prefill_window ? (size_t)(p.tile_end - p.tile_begin) * kWave : (size_t)p.n;
@@ -712,7 +712,7 @@ static hipError_t launch_scan_runs(RawKind raw, const ScanParams& p, const rf_co
 // candidates with 1 % near the query took 0.96 ms where one launch over the tiles takes 0.90; from ~2 M candidates per run on the hand-over wins)
 static bool band_run_qualifies(const ScanParams& p, uint32_t L, uint32_t tiles)
 {
-    static const uint32_t min_run = [] { const char* e = getenv("RF_BAND_RUN_MIN_TILES"); return e ? (uint32_t)atoi(e) : 32768u; }();
+    static const uint32_t min_run = (uint32_t)env_int("RF_BAND_RUN_MIN_TILES", 32768);
     const uint32_t gap = p.len1 > L ? p.len1 - L : L - p.len1;
     return gap <= p.band_k && L >= 80u && tiles >= min_run && tile_bytes(L) <= 0xFFFFFFFFull;  // (80: nothing is handed over below defer_at + 64 columns)
 }
@@ -833,7 +833,7 @@ rf_status run_many(const rf_comparator* c_in, const rf_corpus* corpus_in, rf_op 
 // stream synchronization and four launches); everything else ignores the hint, as before.  Returns false when it does not apply.
 static bool hint_pass_applies(const rf_comparator* c, const rf_corpus* corpus, rf_op op, const rf_args* args, bool f64_out, uint32_t* k1, uint32_t* factor)
 {
-    static const uint32_t min_tiles = [] { const char* e = getenv("RF_HINT_MIN_TILES"); return e ? (uint32_t)atoll(e) : 1024u; }();  // 0xFFFFFFFF: hints are ignored (A/B)
+    static const uint32_t min_tiles = (uint32_t)env_int("RF_HINT_MIN_TILES", 1024);  // 0xFFFFFFFF: hints are ignored (A/B)
     if (f64_out || op != RF_OP_DISTANCE || c->metric != RF_LEVENSHTEIN || args->score_hint_usize == RF_NO_CUTOFF || c->words < 2) return false;
     const uint64_t f = args->insertion_cost;
     if (f < 1 || f > 0xFFFF || args->deletion_cost != f || args->substitution_cost != f) return false;
@@ -868,10 +868,10 @@ static rf_status run_many_hinted(const rf_comparator* c_in, const rf_corpus* cor
     // (default 16384) first run pass 1's scan over every (tiles / 512)-th tile of its length window (ONE launch of the compiled multi-word kernel, which takes a
     // tile step) and count: with fewer than 70 % of the candidates that matter resolved (break-even is ~73 %) the hint is dropped and the plain scan runs.  Costs
     // one more stream synchronization.
-    static const uint32_t sample_min = [] { const char* e = getenv("RF_HINT_SAMPLE_MIN_TILES"); return e ? (uint32_t)atoll(e) : 16384u; }();
+    static const uint32_t sample_min = (uint32_t)env_int("RF_HINT_SAMPLE_MIN_TILES", 16384);
     // (round 6: the sample is skipped while the hint has been proving itself on this corpus -- the pass itself counts what it left unresolved, and that count comes to
     // the host anyway; a hinted call in the steady state then synchronizes once.  A hint that turns bad costs ONE call its first pass, RF_HINT_TRUST=0: sample always.)
-    static const bool trust_on = [] { const char* e = getenv("RF_HINT_TRUST"); return !e || atoi(e) != 0; }();
+    static const bool trust_on = env_on("RF_HINT_TRUST");
     const uint32_t trust = corpus->hint_trust.load(std::memory_order_relaxed);
     const bool trusted = trust_on && trust != 0 && (trust & 15u) != 0;
     if (corpus->n_tiles >= sample_min && !trusted) {
@@ -905,7 +905,7 @@ static rf_status run_many_hinted(const rf_comparator* c_in, const rf_corpus* cor
             }
             const double share = acc[0] ? (double)acc[1] / (double)acc[0] : 0.0;
             const double resolved = in_cut ? share * (double)in_k1 / (double)in_cut : 1.0;
-            static const bool trace_sample = getenv("RF_TRACE_PLAN") != nullptr;
+            const bool trace_sample = sw_trace_plan();
             if (trace_sample) std::fprintf(stderr, "[rf plan] hint sample: %u of %u sampled candidates within max(hint, 31) = %u, ~%.2f of the candidates that matter\n", acc[1], acc[0], k1, resolved);
             if (resolved < 0.70) {
                 corpus->hint_trust.store(0, std::memory_order_relaxed);
@@ -921,7 +921,7 @@ static rf_status run_many_hinted(const rf_comparator* c_in, const rf_corpus* cor
     // wavefront (rf_sparse.hip sparse_words_kernel) -- no mark pass, no sums, no host in between, no copy of the payload (whose reads the second pass now does itself).
     // What the pass left comes back through pinned memory and is read by the NEXT such call (more than 30 % unresolved: the credit is gone and that call takes the road
     // below, with its sample and its count on the host).  RF_HINT_LISTS=0: the road below always.
-    static const bool lists_on = [] { const char* e = getenv("RF_HINT_LISTS"); return !e || atoi(e) != 0; }();
+    static const bool lists_on = env_on("RF_HINT_LISTS");
     const bool sampled_ok = corpus->n_tiles >= sample_min && !trusted;  // (a sample that said no has returned above)
     if (lists_on && (trusted || sampled_ok) && corpus->uniform && !corpus->borrowed && k1 <= 31 && c->words >= 2 && c->words <= (size_t)kMaxWords &&
         corpus->uniform_len >= (uint32_t)kChunk) {
@@ -935,7 +935,7 @@ static rf_status run_many_hinted(const rf_comparator* c_in, const rf_corpus* cor
             p2.pm = p1.pm;
             rf_corpus::TileLease list = corpus->tile_list_lease(st);
             uint32_t *packed_at = nullptr, *first_at = nullptr;
-            p1.tile_list_buf = list ? list->ptr : nullptr;
+            if (list) list->lend(p1);
             bool go = list && band_list_geometry(p1, &packed_at, &first_at);
             volatile uint32_t* report = go ? list->report() : nullptr;
             if (report && report[10] != 0) {  // the last such call on this stream: did its first pass leave more than 30 % of the corpus?
@@ -960,7 +960,7 @@ static rf_status run_many_hinted(const rf_comparator* c_in, const rf_corpus* cor
                 RF_HIP(launch_sparse_words(p2, st));
                 list.release();
                 corpus->hint_trust.store(std::min<uint32_t>(trust + 1, 0x7FFFFFFFu), std::memory_order_relaxed);
-                static const bool trace_lists = getenv("RF_TRACE_PLAN") != nullptr;
+                const bool trace_lists = sw_trace_plan();
                 if (trace_lists) std::fprintf(stderr, "[rf plan] hint lists: k1=%u, the band pass lists what it leaves, %u-word scan over the list\n", k1, p2.words);
                 if (out_mem == RF_MEM_HOST) RF_HIP(copy_home(out, d_out, out_bytes, st));
                 return RF_OK;
@@ -1010,7 +1010,7 @@ static rf_status run_many_hinted(const rf_comparator* c_in, const rf_corpus* cor
         bytes2 += t * tile_bytes(corpus->lengths[r]);
     }
     tile_base[R] = (uint32_t)tiles2_64;
-    static const bool trace_plan = getenv("RF_TRACE_PLAN") != nullptr;
+    const bool trace_plan = sw_trace_plan();
     if (trace_plan) std::fprintf(stderr, "[rf plan] hint pass: k1=%u, %llu dense tiles (%llu bytes) of %u left for the full scan\n", k1, (unsigned long long)tiles2_64, (unsigned long long)bytes2, corpus->n_tiles);
     // what the pass left, for the next hinted call on this corpus: at most 30 % unresolved (the sample's own line) and the hint keeps its credit
     if ((uint64_t)run_prefix[R] * 10 <= (uint64_t)corpus->n * 3)
@@ -1105,13 +1105,13 @@ rf_status run_many(const rf_comparator* c_in, const rf_corpus* corpus_in, rf_op 
     // normalized_distance / normalized_similarity of a multi-word Levenshtein scan: the u32 distance scan (the asm kernels with the
     // Ukkonen band: 3.3 instead of 2.5 Gpairs/s at 256 x 256) into a temporary, then ONE pass that runs the very arithmetic of emit_fin (rf_device.hpp) on every
     // distance -- dist / maximum, 1.0 - nd, the cutoff compare -- 12 bytes per candidate against a scan of >= 128 symbols each.  RF_NORM_TWO_STEP=0: the A/B switch.
-    static const bool norm_two_step = [] { const char* e = getenv("RF_NORM_TWO_STEP"); return !e || atoi(e) != 0; }();
+    static const bool norm_two_step = env_on("RF_NORM_TWO_STEP");
     // (round 6) ... and under an f64 cutoff that leaves at most 31 raw edits -- normalized_similarity >= 0.9 of a 256-symbol query: 25 -- the u32 scan runs under THAT
     // cutoff, i.e. the small-band kernel (rf_band.hip: 75 Gpairs/s where the compiled f64 early-out scan walks four words per column), and the normalizing pass decides
     // Some / None from the exact distance as before.  The raw cutoff is the largest distance the f64 test can pass for the longest candidate, plus one edit of slack for
     // the rounding of c x maximum: whatever the band answers None is beyond it, and None stays None (details/distance.rs:246-250, :273; common.rs:43-45).
     // RF_NORM_BAND=0: the compiled f64 scan.
-    static const bool norm_band = [] { const char* e = getenv("RF_NORM_BAND"); return !e || atoi(e) != 0; }();
+    static const bool norm_band = env_on("RF_NORM_BAND");
     uint64_t norm_raw_cut = RF_NO_CUTOFF;
     if (norm_band && f64_out && raw == RAW_LEV && p.has_cutoff && p.finish == FIN_LEV && p.factor >= 1 && c->words >= 2 &&
         (op == RF_OP_NORMALIZED_DISTANCE || op == RF_OP_NORMALIZED_SIMILARITY)) {
@@ -1150,7 +1150,7 @@ rf_status run_many(const rf_comparator* c_in, const rf_corpus* corpus_in, rf_op 
                   : nullptr;
     if (p.data6) p.max_stored_sym = corpus_max_stored_symbol(corpus, st);  // (< 63: the scans may zero the table row of the fill code)
     if (corpus->uniform) plan_band_filter(c, corpus, op, f64_out, &p, corpus->uniform_len);  // (bucketed corpora: per length run, launch_scan_runs)
-    static const bool jaro_priv = [] { const char* e = getenv("RF_JARO_PRIV"); return e && atoi(e) != 0; }();  // (off by default: rf_jaro.hip launch_jaro_word)
+    const bool jaro_priv = sw_jaro_priv();  // (off by default: rf_jaro.hip launch_jaro_word)
     if (jaro_priv && raw == RAW_JARO && corpus->uniform && !p.has_cutoff) p.max_stored_sym = corpus_max_stored_symbol(corpus, st);
     const size_t elem = f64_out ? sizeof(double) : sizeof(uint32_t);
     const size_t out_bytes = (want_slots ? corpus->n_slots : corpus->n) * elem;
@@ -1182,7 +1182,7 @@ rf_status run_many(const rf_comparator* c_in, const rf_corpus* corpus_in, rf_op 
         p.tiles = corpus->d_tiles_by_origin;
         p.xcd_deal = tile_order >= 2 ? 1u : 0u;
     }
-    static const size_t unscatter_min = [] { const char* e = getenv("RF_UNSCATTER_MIN"); return e ? (size_t)atoll(e) : (size_t)1 << 20; }();
+    static const size_t unscatter_min = (size_t)env_int("RF_UNSCATTER_MIN", 1048576);
     void* d_tmp = nullptr;  // this stream's kept buffer of the corpus, or a block of `sc` for the call
     StreamCache<rf_corpus::GatherTmp>::Lease kept;  // (held while the scan + gather are enqueued)
     const rf_corpus::GatherMaps* maps = nullptr;
@@ -1235,23 +1235,23 @@ rf_status run_many(const rf_comparator* c_in, const rf_corpus* corpus_in, rf_op 
     // (... and the small-band scans of a single-length corpus: tiles with a few lanes left are listed for a dense second pass, rf_band.hip launch_band)
     const bool band_lists = p.band && raw == RAW_LEV && corpus->uniform && !p.tiles && !want_slots && p.tile_step == 1 && !by_runs;
     // (... and of a bucketed corpus: its long length runs are walked as single-length corpora of their own, launch_band_runs.  RF_BAND_RUNS=0: one launch over the tiles)
-    static const bool band_runs_on = [] { const char* e = getenv("RF_BAND_RUNS"); return !e || atoi(e) != 0; }();
+    static const bool band_runs_on = env_on("RF_BAND_RUNS");
     const bool band_runs = band_runs_on && p.band && raw == RAW_LEV && !corpus->uniform && p.tiles == corpus->d_tiles && corpus->d_orig != nullptr && !want_slots &&
                            p.tile_step == 1 && !by_runs && !by_origin && !p.topk_k && band_has_long_run(p, corpus);
     int band_runs_mode = 2;  // 2: every long run through launch_band, 1: the longest one only, 0: none (one launch over the tiles)
     if (p.heads8 || band_lists || band_runs) {  // (the head-plane scans: band prefilter or first look as a streaming pass, then the cutoff scan over its list)
         tl = corpus->tile_list_lease(st);
-        p.tile_list_buf = tl ? tl->ptr : nullptr;
+        if (tl) tl->lend(p);
         p.lane_list = tl ? 1u : 0u;
         if ((band_lists || band_runs) && tl) {
-            p.band_defer_seen = tl->ptr + tl->words - 4;
+            p.band_defer_seen = tl->ptr + ListLayout::trailer_at(tl->words);
             // Which form this launch takes.  Handing tiles over pays when many tiles hold a few near candidates; on a corpus with none, or with most lanes of most tiles
             // near, it buys nothing and costs the list kernels and ~3 % of the first pass' columns.  The second pass of this stream's LAST hand-over launch left what it
             // listed in pinned memory (E tiles, S lanes, of N tiles at column a); read here without waiting -- whatever launch it is from, it only steers speed:
             //   columns saved ~ E (L - a) - S / 64 L   against   N a + (tiles alive at a) (L - a)  of the plain launch
             // (tiles alive at a: the listed ones, or -- when the listed ones sit right at the lane limit, so that most live tiles are above it -- all of them).
             // Below 25 % the plain kernel runs, and every 16th launch looks again.  RF_BAND_DEFER_ADAPT=0: always hand over.
-            static const bool adapt = [] { const char* e = getenv("RF_BAND_DEFER_ADAPT"); return !e || atoi(e) != 0; }();
+            static const bool adapt = env_on("RF_BAND_DEFER_ADAPT");
             volatile uint32_t* report = tl->report();
             p.band_report = const_cast<uint32_t*>(report);
             if (adapt && report) {
@@ -1274,7 +1274,7 @@ rf_status run_many(const rf_comparator* c_in, const rf_corpus* corpus_in, rf_op 
             }
         }
     }
-    static const bool trace_plan = getenv("RF_TRACE_PLAN") != nullptr;  // one line per rf_many_* call on stderr: which path the plan took
+    const bool trace_plan = sw_trace_plan();  // one line per rf_many_* call on stderr: which path the plan took
     if (trace_plan)
         std::fprintf(stderr, "[rf plan] raw=%d words=%u early=%u first_check=%u band=%u heads8=%d head_need=%u head_k=%u tile_list=%d by_runs=%d by_origin=%d gather=%d "
                              "tiles=[%u,%u) of %u prefill=%u data6=%d\n",

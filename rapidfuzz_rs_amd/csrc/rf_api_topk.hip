@@ -81,7 +81,7 @@ static rf_status topk_core(const rf_comparator* c_in, const rf_corpus* corpus_in
     // 20 M ragged corpus where the pass's fixed ~0.2 ms shows: profiles/topk_via_scores_r04.txt).  The score vector is the caller's
     // `out_all` when there is one, else a buffer kept per (corpus, stream) like the rest of the top-k scratch.
     // RF_TOPK_VIA_SCORES: 0 = never, 1 = default, 2 = every shape with an asm scan (tests).
-    static const int via_scores = [] { const char* e = getenv("RF_TOPK_VIA_SCORES"); return e ? atoi(e) : 1; }();
+    static const int via_scores = (int)env_int("RF_TOPK_VIA_SCORES", 1);
     const bool asm_scan = !p.early && !p.band && !p.long_words_pad && p.tile_step == 1 && ((raw == RAW_LEV && p.words <= 4) || (raw == RAW_OSA && p.words == 1));
     if (asm_scan && (via_scores >= 2 || (via_scores == 1 && raw == RAW_LEV && p.words >= 2))) {
         uint32_t* d_scores = d_all;
@@ -103,7 +103,7 @@ static rf_status topk_core(const rf_comparator* c_in, const rf_corpus* corpus_in
     rf_corpus::TileLease list;
     if (p.heads8) {
         list = corpus->tile_list_lease(st);
-        p.tile_list_buf = list ? list->ptr : nullptr;
+        if (list) list->lend(p);
         p.lane_list = list ? 1u : 0u;
     }
     hipError_t e = hipSuccess;
@@ -113,7 +113,7 @@ static rf_status topk_core(const rf_comparator* c_in, const rf_corpus* corpus_in
     // tight cutoff (p.early) the cutoff itself keeps nearly everything out of the lists and the pass is skipped.
     // Each launch selects its own k best in its last workgroup (topk_block_publish): 2 launches, or 1.
     // (RF_TOPK_SAMPLE=<tiles> tunes the sample size, 0 disables the pass: A/B switch)
-    static const uint32_t kSampleTiles = [] { const char* e = getenv("RF_TOPK_SAMPLE"); return e ? (uint32_t)atoi(e) : 1024u; }();
+    static const uint32_t kSampleTiles = (uint32_t)env_int("RF_TOPK_SAMPLE", 1024);
     if (kSampleTiles && !p.early && p.tile_end - p.tile_begin >= 8 * kSampleTiles) {
         ScanParams ps = p;
         ps.out = nullptr;
@@ -179,7 +179,8 @@ static rf_status select_topk(const void* d_scores, bool f64, bool desc, uint32_t
             cum += hist[d];
         }
         if (d == (1u << bits)) {
-            if (getenv("RF_SELECT_DEBUG")) {
+            static const bool select_debug = env_set("RF_SELECT_DEBUG");
+            if (select_debug) {
                 unsigned long long tot = 0;
                 for (auto h : hist) tot += h;
                 std::fprintf(stderr, "[select] min %llx max %llx valid %llu kk %llu hb %d shift %u bits %u prefix %llx mask %llx rank %llu cum %llu total-in-hist %llu\n",

@@ -165,7 +165,7 @@ __device__ __forceinline__ void band_stage_table(const ScanParams& p, uint32_t* 
 }
 
 // kDefer (single-length corpora, round 6): tiles that still hold a few live lanes at column p.band_defer_at are LISTED (tile, lane mask: the 16-byte entries of
-// rf_scan.hip's lane lists, one segment of `cap` entries per wavefront, counts at buf + 4) instead of being run to the end for those few.
+// rf_scan.hip's lane lists, one segment of `cap` entries per wavefront: ListLayout, lanes form) instead of being run to the end for those few.
 template <bool kUniform, bool kDefer, bool kList = false>
 __device__ __forceinline__ void band_kernel_body(const ScanParams& p, uint32_t* __restrict__ buf, uint32_t cap)
 {
@@ -179,7 +179,8 @@ __device__ __forceinline__ void band_kernel_body(const ScanParams& p, uint32_t* 
     const uint32_t pitch_bytes = stride * 4u;
     const bool asm_run = p.band_asm != 0;  // (RF_ASM_BAND=0: the compiled column everywhere, the A/B switch)
     const uint32_t gw = blockIdx.x * kWavesPerBlock + wave, n_waves = gridDim.x * kWavesPerBlock;
-    uint4* seg = (kDefer || kList) ? reinterpret_cast<uint4*>(buf + 4 + 2 * (size_t)n_waves) + (size_t)gw * cap : nullptr;
+    const ListLayout L = ListLayout::of_launch(ListLayout::kLanes, n_waves, cap);
+    uint4* seg = (kDefer || kList) ? reinterpret_cast<uint4*>(L.segment(buf, gw)) : nullptr;
     uint32_t kept = 0, kept_lanes = 0;
     bool open = p.band_defer_after == 0;  // this wavefront has seen the launch's count of hand-over candidates reached (0: nothing to count)
     for (uint32_t t = p.tile_begin + gw; t < p.tile_end; t += n_waves) {
@@ -208,7 +209,7 @@ __device__ __forceinline__ void band_kernel_body(const ScanParams& p, uint32_t* 
         }
     }
     if constexpr (kDefer || kList) {
-        if (lane == 0) reinterpret_cast<uint2*>(buf + 4)[gw] = make_uint2(kept, kept_lanes);
+        if (lane == 0) reinterpret_cast<uint2*>(buf + L.wave_counts_at())[gw] = make_uint2(kept, kept_lanes);
     }
 }
 
@@ -240,7 +241,7 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void band_sparse_kernel(cons
 {
     extern __shared__ uint32_t lds_band[];
     const uint4* __restrict__ list = reinterpret_cast<const uint4*>(p.tile_list);
-    const uint32_t entries = uniform(p.tile_list_count[0]), total = uniform(p.tile_list_count[1]);
+    const uint32_t entries = uniform(p.tile_list_count[0]), total = uniform(p.tile_list_count[ListLayout::kLaneSurvivorsAt]);
     const uint32_t n_dense = (total + kWave - 1) / kWave;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         if (p.band_defer_seen) *p.band_defer_seen = 0;  // (the first pass' count of hand-over candidates: zero again for this stream's next launch)
@@ -288,16 +289,31 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void band_sparse_kernel(cons
     }
 }
 
+// every workgroup stages the 32-bit band table (256 x (2W + 5) dwords: 13 KiB at 256 symbols) before its first tile, and a
+// tile dies after 8-16 columns: half the general launches' workgroups per CU measured best (configs[2] corpus, cutoff 8:
+// 8 or 16 per CU 76.7 Gpairs/s, 24: 72.7, 32: 67.8, 64: 55.5)
+static int band_grid_of(const ScanParams& p) { return std::max(1, std::min(scan_grid(p.tile_end - p.tile_begin), (scan_max_grid() + 1) / 2)); }
+// the lists of a listing band launch over p's tiles: a segment per wavefront of that grid
+static ListLayout band_list_layout(const ScanParams& p) { return ListLayout::band(p.tile_end - p.tile_begin, (uint32_t)band_grid_of(p) * kWavesPerBlock); }
+
+// where a band_list launch over p's tiles leaves its packed list and first[] inside p.tile_list_buf (false: such a launch does not fit the buffer)
+bool band_list_geometry(const ScanParams& p, uint32_t** packed_at, uint32_t** first_at)
+{
+    if (p.tile_end <= p.tile_begin || !p.tile_list_buf) return false;
+    const ListLayout L = band_list_layout(p);
+    if (!L.fits(p.tile_list_words)) return false;
+    *packed_at = p.tile_list_buf + L.packed_at();
+    *first_at = p.tile_list_buf + L.first_at();
+    return true;
+}
+
 hipError_t launch_band(const ScanParams& p, hipStream_t stream)
 {
     if (p.tile_end <= p.tile_begin) return hipSuccess;
     const size_t lds = (size_t)256 * band_row_dwords(p.words) * sizeof(uint32_t);
-    // every workgroup stages the 32-bit band table (256 x (2W + 5) dwords: 13 KiB at 256 symbols) before its first tile, and a
-    // tile dies after 8-16 columns: half the general launches' workgroups per CU measured best (configs[2] corpus, cutoff 8:
-    // 8 or 16 per CU 76.7 Gpairs/s, 24: 72.7, 32: 67.8, 64: 55.5)
-    const int band_grid = std::max(1, std::min(scan_grid(p.tile_end - p.tile_begin), (scan_max_grid() + 1) / 2));
+    const int band_grid = band_grid_of(p);
     const dim3 g(band_grid), b(kWave * kWavesPerBlock);
-    static const bool use_asm = [] { const char* e = getenv("RF_ASM_BAND"); return !e || atoi(e) != 0; }();
+    static const bool use_asm = env_on("RF_ASM_BAND");
     ScanParams pa = p;
     pa.band_asm = use_asm ? 1u : 0u;
     // LANE COMPACTION (single-length corpora): on a corpus where a good share of the candidates IS near the query no tile dies -- every one of
@@ -305,34 +321,32 @@ hipError_t launch_band(const ScanParams& p, hipStream_t stream)
     // band_defer_at (a random candidate is past break_score by then) unless most of its lanes are still in, and band_sparse_kernel runs the listed lanes 64 to a
     // wavefront from column 0.  RF_BAND_DEFER=0 switches it off, RF_BAND_DEFER_AT / RF_BAND_DEFER_MAX move the column and the lane count (default k + 8 rounded up to a whole chunk / 44),
     // RF_BAND_DEFER_AFTER the number of such tiles a launch runs in place first (0).
-    static const bool defer_on = [] { const char* e = getenv("RF_BAND_DEFER"); return !e || atoi(e) != 0; }();
-    static const uint32_t defer_at_env = [] { const char* e = getenv("RF_BAND_DEFER_AT"); return e ? ((uint32_t)atoi(e) + 15u) / 16u * 16u : 0u; }();
-    static const uint32_t defer_max = [] { const char* e = getenv("RF_BAND_DEFER_MAX"); return e ? (uint32_t)atoi(e) : 44u; }();
+    static const bool defer_on = env_on("RF_BAND_DEFER");
+    static const uint32_t defer_at_env = ((uint32_t)env_int("RF_BAND_DEFER_AT", 0) + 15u) / 16u * 16u;
+    static const uint32_t defer_max = (uint32_t)env_int("RF_BAND_DEFER_MAX", 44);
     // (0 since the launch form follows the last launch's report, rf_api_scan.hip: a corpus with a handful of near candidates takes the plain kernel on 15 launches of 16,
     // and counting cost the others one same-address atomic per wavefront -- 16 K of them at the start of the launch, 250 -> 190 us at 1 % near candidates)
-    static const uint32_t defer_after = [] { const char* e = getenv("RF_BAND_DEFER_AFTER"); return e ? (uint32_t)atoi(e) : 0u; }();
+    static const uint32_t defer_after = (uint32_t)env_int("RF_BAND_DEFER_AFTER", 0);
     // (the column: a candidate unrelated to the query adds nearly one to its score per column from k on and is out past break_score = 2k (+ the length difference):
     // k + 8 columns see the random lanes off, rounded up to a chunk end -- 16 at k = 8, 48 at the k = 31 of a hinted scan's first pass.  Where they last longer
     // -- four-symbol alphabets -- the tile is simply not sparse yet at that column and runs on in place.)
     const uint32_t defer_at = defer_at_env ? defer_at_env : std::min(64u, std::max(16u, (p.band_k + 8u + 15u) / 16u * 16u));
-    const uint32_t G = (uint32_t)band_grid * kWavesPerBlock, n_tiles = p.tile_end - p.tile_begin;
+    const ListLayout L = band_list_layout(p);
+    uint32_t* const buf = p.tile_list_buf;
     if (p.band_list) {  // (the caller has checked band_list_geometry() and holds the list buffer; it launches the second pass itself)
-        if (!p.tile_list_buf || p.tiles || G > 16384u) return hipErrorInvalidValue;
-        const uint32_t cap = (n_tiles + G - 1) / G;
+        if (!buf || p.tiles || !L.fits(p.tile_list_words)) return hipErrorInvalidValue;
         if (lds > 48 * 1024) {
             const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(band_list_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             if (e != hipSuccess) return e;
         }
-        hipLaunchKernelGGL(band_list_kernel, g, b, lds, stream, pa, p.tile_list_buf, cap);
+        hipLaunchKernelGGL(band_list_kernel, g, b, lds, stream, pa, buf, L.cap);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
-        uint32_t* packed_at = p.tile_list_buf + 4 + 2 * (size_t)G + 4 * (size_t)G * cap;
-        return launch_lane_list_pack(p.tile_list_buf, G, cap, packed_at + 4 * ((size_t)n_tiles + 2), stream);
+        return launch_lane_list_pack(buf, L.G, L.cap, buf + L.first_at(), stream);
     }
-    const bool defer = defer_on && defer_at && p.lane_list && p.tile_list_buf && p.band_defer_seen && !p.tiles && G <= 16384u && p.uniform_len >= defer_at + 64u &&
+    const bool defer = defer_on && defer_at && p.lane_list && buf && p.band_defer_seen && !p.tiles && L.fits(p.tile_list_words) && p.uniform_len >= defer_at + 64u &&
                        p.len1 >= defer_at + 64u + p.band_k;
     if (defer) {
-        const uint32_t cap = (n_tiles + G - 1) / G;  // the tiles one wavefront walks
         pa.band_defer_at = defer_at;
         pa.band_defer_max = std::min(defer_max, 63u);
         pa.band_defer_after = defer_after;
@@ -341,17 +355,15 @@ hipError_t launch_band(const ScanParams& p, hipStream_t stream)
             if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(band_sparse_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             if (e != hipSuccess) return e;
         }
-        hipLaunchKernelGGL(band_defer_kernel, g, b, lds, stream, pa, p.tile_list_buf, cap);
+        hipLaunchKernelGGL(band_defer_kernel, g, b, lds, stream, pa, buf, L.cap);  // (cap: the tiles one wavefront walks)
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
-        uint32_t* packed_at = p.tile_list_buf + 4 + 2 * (size_t)G + 4 * (size_t)G * cap;
-        uint32_t* first_at = packed_at + 4 * ((size_t)n_tiles + 2);
-        e = launch_lane_list_pack(p.tile_list_buf, G, cap, first_at, stream);
+        e = launch_lane_list_pack(buf, L.G, L.cap, buf + L.first_at(), stream);
         if (e != hipSuccess) return e;
         ScanParams p2 = pa;
-        p2.tile_list = packed_at;
-        p2.lane_first = first_at;
-        p2.tile_list_count = p.tile_list_buf;
+        p2.tile_list = buf + L.packed_at();
+        p2.lane_first = buf + L.first_at();
+        p2.tile_list_count = buf + L.count_at();
         // (half the first pass' grid: the workgroups beyond the survivors leave at once, but launching them is 2 us of an empty second pass)
         hipLaunchKernelGGL(band_sparse_kernel, dim3(std::max(1, band_grid / 2)), b, lds, stream, p2);
         return hipGetLastError();
@@ -363,19 +375,6 @@ hipError_t launch_band(const ScanParams& p, hipStream_t stream)
     }
     hipLaunchKernelGGL(kern, g, b, lds, stream, pa);
     return hipGetLastError();
-}
-
-// where a band_list launch over p's tiles leaves its packed list and first[] inside p.tile_list_buf (false: such a launch does not fit the buffer's 16 K segments)
-bool band_list_geometry(const ScanParams& p, uint32_t** packed_at, uint32_t** first_at)
-{
-    if (p.tile_end <= p.tile_begin || !p.tile_list_buf) return false;
-    const uint32_t n_tiles = p.tile_end - p.tile_begin;
-    const int band_grid = std::max(1, std::min(scan_grid(n_tiles), (scan_max_grid() + 1) / 2));
-    const uint32_t G = (uint32_t)band_grid * kWavesPerBlock, cap = (n_tiles + G - 1) / G;
-    if (G > 16384u) return false;
-    *packed_at = p.tile_list_buf + 4 + 2 * (size_t)G + 4 * (size_t)G * cap;
-    *first_at = *packed_at + 4 * ((size_t)n_tiles + 2);
-    return true;
 }
 
 }  // namespace rf

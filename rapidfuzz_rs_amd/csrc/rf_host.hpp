@@ -302,11 +302,8 @@ struct rf_corpus {
     // hipMallocAsync / hipFreeAsync pair per call made the SUBMISSION of such a step wait for the previous step (measured: 560 us per
     // call to submit a 575 us step; 11 us with the buffer kept).
     using GatherTmp = DeviceBuf;
-    // head_filter_kernel's tile list (rf_scan.hip), the lane lists and the small-band hand-over's (rf_band.hip).  Words: round 5's
-    // layout (packed count, <= 16 K per-wavefront counts and offsets, their segments -- n_tiles + 2 per wavefront of rounding --, the
-    // packed list) needs 2 n_tiles + 5 x 16384; the lane lists (lane_list_pack_kernel: 16-byte entries in the segments and in the
-    // packed list) four times the entries, + one word per dense tile (its first[]); the last 4 words: launch_band's count of
-    // hand-over candidates, zero between launches.
+    // head_filter_kernel's tile list (rf_scan.hip), the lane lists and the small-band hand-over's (rf_band.hip): ListLayout (rf_list_layout.hpp) describes the
+    // buffer, sizes it for every launch shape, and keeps its trailer (launch_band's count of hand-over candidates, zero between launches).
     struct TileList : NoCopy {
         uint32_t* ptr = nullptr;
         size_t words = 0;
@@ -320,11 +317,11 @@ struct rf_corpus {
         }
         hipError_t make(uint32_t n_tiles, hipStream_t st)
         {
-            const size_t w = 9 * (size_t)n_tiles + 12 * 16384 + 64;
+            const size_t w = ListLayout::words_needed(n_tiles);
             const hipError_t e = hipMalloc((void**)&ptr, w * sizeof(uint32_t));
             if (e != hipSuccess) return e;
             words = w;
-            if (hipMemsetAsync(ptr + words - 4, 0, 4 * sizeof(uint32_t), st) != hipSuccess) (void)hipGetLastError();
+            if (hipMemsetAsync(ptr + ListLayout::trailer_at(words), 0, ListLayout::kTrailerWords * sizeof(uint32_t), st) != hipSuccess) (void)hipGetLastError();
             return hipSuccess;
         }
         volatile uint32_t* report()  // band_report, allocated on first use; nullptr = no pinned memory to be had
@@ -337,6 +334,11 @@ struct rf_corpus {
             return band_report;
         }
         uint64_t bytes() const { return (uint64_t)words * sizeof(uint32_t); }
+        void lend(ScanParams& p) const  // the buffer and its size, for the launchers' ListLayout::fits()
+        {
+            p.tile_list_buf = ptr;
+            p.tile_list_words = (uint32_t)std::min<size_t>(words, 0xFFFFFFFFu);
+        }
     };
     mutable StreamCache<TopkScratch> topk_scratch{8, true};  // (on `parent` for a translated image)
     mutable StreamCache<GatherTmp> gather_tmp{4, false};     // (a fifth stream: a stream-ordered allocation for the call)

@@ -4,10 +4,12 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include <string>
 
 #include "../../include/rfgpu.h"
+#include "rf_list_layout.hpp"
 
 namespace rf {
 
@@ -105,7 +107,8 @@ struct ScanParams {
     uint32_t tile_step;             // >= 1: visit every tile_step-th tile of the range (the top-k bound sample)
     uint32_t head_need, head_k;     // head-plane cutoff scans: >= head_need of the first 8 symbols must have a partner within head_k positions (0 = filter off)
     // head_filter_kernel's product: the tiles a cutoff scan still has to walk ([0] = their number, then the tiles); tile_list_buf is
-    // the scratch the launcher may use for it (n_tiles + 1 words), tile_list / tile_list_count what early_lean_kernel reads
+    // the stream's list buffer the launcher may use for it (ListLayout, rf_list_layout.hpp), tile_list / tile_list_count what early_lean_kernel reads
+    uint32_t tile_list_words;  // HOST side only: the size of tile_list_buf, for ListLayout::fits()
     uint32_t* tile_list_buf;
     const uint32_t* tile_list;
     const uint32_t* tile_list_count;
@@ -116,7 +119,7 @@ struct ScanParams {
     uint32_t lane_list;
     const uint32_t* lane_first;  // sparse_lean_kernel: per dense tile j the packed entry that holds survivor 64 j (lane_list_pack_kernel writes it)
     // ... and where the survivors' results go when the caller wants no dense vector (rf_filter_*): lane_val[g] (u32 or f64 by out_f64; None = beyond the cutoff) and
-    // lane_idx[g] = candidate index for survivor g < lane_cap (the number of survivors -- tile_list_buf[1] -- may exceed lane_cap: the host then takes another road)
+    // lane_idx[g] = candidate index for survivor g < lane_cap (the number of survivors -- ListLayout::kLaneSurvivorsAt -- may exceed lane_cap: the host then takes another road)
     void* lane_val;
     uint32_t* lane_idx;
     uint32_t lane_cap;
@@ -154,7 +157,7 @@ struct ScanParams {
     uint32_t band, band_k;
     uint32_t band_asm;              // 1: full eight-column diagonal runs as one asm block (rf_band_asm.inc; set by the launcher)
     uint32_t band_defer_at, band_defer_max, band_defer_after;  // != 0 (set by the launcher): a tile with <= band_defer_max lanes within break_score at column band_defer_at is listed for band_sparse_kernel, once the launch has seen band_defer_after of them
-    uint32_t* band_defer_seen;      // that count (the last words of the stream's tile-list buffer; band_sparse_kernel zeroes it again)
+    uint32_t* band_defer_seen;      // that count (the list buffer's trailer, ListLayout::trailer_at(); band_sparse_kernel zeroes it again)
     uint32_t* band_report;          // pinned host words (or nullptr): band_sparse_kernel leaves [0] tiles listed, [1] lanes listed, [2] tiles of the launch, [3] 1, [4] band_defer_at, [5] band_defer_max, [6] the launch's candidate length; [8..10]: sparse_words_kernel's (lanes listed, candidates, 1)
     uint32_t band_list;             // 1 (score_hint, first pass): the band launch lists every tile that holds lanes it answered None, with their mask (tile_list_buf), for launch_sparse_words
     // the multi-word asm scans (rf_stream_asm.hip, tools/gen_stream_asm.py BlockKind): raw distances above trim_k1 - 1 need not be exact (they must come out above
@@ -190,11 +193,22 @@ hipError_t launch_hint_gather(const ScanParams& p, const uint32_t* run_first, ui
                               const uint32_t* run_tile_base, const uint64_t* run_data_base, const uint32_t* run_len, uint32_t n_tiles2, uint8_t* data2, TileDesc* tiles2,
                               uint32_t* orig2, hipStream_t st);
 hipError_t launch_band(const ScanParams& p, hipStream_t stream);  // rf_band.hip: exact tiles [tile_begin, tile_end)
-bool band_list_geometry(const ScanParams& p, uint32_t** packed_at, uint32_t** first_at);  // rf_band.hip: where a p.band_list launch leaves its packed list / first[] in p.tile_list_buf
+bool band_list_geometry(const ScanParams& p, uint32_t** packed_at, uint32_t** first_at);  // rf_band.hip: where a p.band_list launch leaves its packed list / first[] in p.tile_list_buf (false: it does not fit)
 // rf_sparse.hip: the lane compaction of the head-plane cutoff scans (ScanParams::lane_list)
 hipError_t launch_sparse_lean(int state_kind, const ScanParams& p, hipStream_t stream);  // state_kind: 0 LevState<1>, 1 Lev32State, 2 OsaState<1>; p.tile_list = the packed 16-byte entries
 hipError_t launch_sparse_words(const ScanParams& p, hipStream_t stream);  // rf_sparse.hip: the multi-word Levenshtein scan (p.words = 2..8, single-length corpus) over the listed lanes
-bool head_two_pass_applies(RawKind raw, const ScanParams& p);  // rf_scan.hip: will launch_scan take head_filter_kernel + a second pass for this launch?
+// rf_scan.hip: the road launch_scan takes for a single-word cutoff scan (p.early, p.words == 1, Levenshtein / LCS / OSA, neither band nor long pattern) -- decided
+// here ONCE: launch_state launches from the answer, and a caller that must know before it launches (rf_filter_* hands the lanes road a compact result) asks the same.
+enum class EarlyRoad {
+    RunTime,       // scan_kernel: `early` and the look's column read from ScanParams at run time (RF_EARLY_STATIC=0, or a column with no compiled form)
+    Tiles,         // early_kernel over tile descriptors
+    Uniform,       // early_kernel over a single-length corpus (RF_EARLY_LEAN=0, or candidates shorter than a chunk)
+    Lean,          // early_lean_kernel
+    Head8,         // early_head8_kernel: the first look from the head plane, inside the cutoff kernel
+    TwoPassTiles,  // head_filter_kernel + tile_list_pack_kernel, then early_lean_kernel over the surviving tiles
+    TwoPassLanes   // head_filter_kernel + lane_list_pack_kernel, then rf_sparse.hip over the surviving lanes
+};
+EarlyRoad early_road(RawKind raw, const ScanParams& p);
 hipError_t launch_lane_list_pack(uint32_t* buf, uint32_t G, uint32_t cap, uint32_t* first_of, hipStream_t stream);  // rf_scan.hip lane_list_pack_kernel over G segments of `cap` entries
 hipError_t launch_scan_mixed(RawKind raw, const ScanParams& p, hipStream_t stream);  // p.mixed / tile_begin / tile_end: the mixed section
 hipError_t launch_long(RawKind raw, const ScanParams& p, hipStream_t stream, int grid);
@@ -281,5 +295,28 @@ int scan_grid(uint32_t n_tiles);       // the grid of short-running launches ove
 int scan_grid_full(uint32_t n_tiles);  // the grid of full (no-cutoff) scans; >= scan_grid
 
 void set_error(const std::string& msg);
+
+// Environment switches (the table in include/rfgpu.h; tests/test_docs.py holds the two together).  Three parsers; every reader keeps what it read in a function-local
+// static, so a variable is read once per process, on first use.  A variable with readers in more than one place has ONE accessor below.
+inline bool env_on(const char* name)  // on unless set to 0
+{
+    const char* e = getenv(name);
+    return !e || atoi(e) != 0;
+}
+inline bool env_set(const char* name) { return getenv(name) != nullptr; }  // set, whatever the value
+inline long long env_int(const char* name, long long dflt)
+{
+    const char* e = getenv(name);
+    return e ? atoll(e) : dflt;
+}
+inline bool sw_asm_chunk() { static const bool v = env_on("RF_ASM_CHUNK"); return v; }
+inline bool sw_jaro_priv() { static const bool v = env_int("RF_JARO_PRIV", 0) != 0; return v; }  // (off by default: rf_jaro.hip launch_jaro_word)
+inline bool sw_no_mixed_tiles() { static const bool v = env_set("RF_NO_MIXED_TILES"); return v; }
+inline bool sw_pack_timing() { static const bool v = env_set("RF_PACK_TIMING"); return v; }
+inline bool sw_trace_plan() { static const bool v = env_set("RF_TRACE_PLAN"); return v; }  // one line per call on stderr: which path the plan took
+inline bool sw_stream_timing() { static const bool v = env_set("RF_STREAM_TIMING"); return v; }  // phase times of a streamed scan on stderr
+#ifdef RF_EXPERIMENTS  // measurement builds only (tools/build_stream_variant.sh): the shipping library has no switch that changes a result
+inline bool sw_exp_nohbm() { static const bool v = env_set("RF_EXP_NOHBM"); return v; }  // every tile reads tile 0's bytes (results are wrong on purpose)
+#endif
 
 }  // namespace rf

@@ -986,7 +986,7 @@ static hipError_t launch_jaro_word(const ScanParams& p, ScanParams q, hipStream_
     auto k = p.tiles ? (early ? jaro_word_kernel<false, true> : (fast ? jaro_word_fast_kernel<false> : jaro_word_kernel<false, false>))
                      : (early ? jaro_word_kernel<true, true> : (fast ? jaro_word_fast_kernel<true> : jaro_word_kernel<true, false>));
     // the hand-scheduled kernel: single-length corpus, table epilogue, truncated candidate length a multiple of 16
-    static const bool use_asm = [] { const char* e = getenv("RF_ASM_CHUNK"); return !e || atoi(e) != 0; }();
+    const bool use_asm = sw_asm_chunk();
     bool asm_ok = use_asm && fast && !early && !p.tiles && p.len1 >= 2;
     if (asm_ok) {
         uint32_t len1 = p.len1, len2 = p.uniform_len, bound = 0;  // jaro.rs:550-565, as in the kernel
@@ -999,7 +999,7 @@ static hipError_t launch_jaro_word(const ScanParams& p, ScanParams q, hipStream_
     // RF_JARO_PRIV=1: the conflict-free table copy for corpora of <= 64 stored symbols.  OFF by default -- measured, it buys nothing
     // (profiles/jaro_lds_r04.txt: bank conflicts 400 M -> 0.5 M, LDS-active cycles -38 %, SQ_WAIT_INST_LDS -46 %, and the same 2.94 ms:
     // the kernel is bound by VALU issue, not by the LDS, and the copy's 16 KiB cost it one resident workgroup per CU)
-    static const bool use_priv = [] { const char* e = getenv("RF_JARO_PRIV"); return e && atoi(e) != 0; }();
+    const bool use_priv = sw_jaro_priv();
     if (asm_ok && use_priv && p.max_stored_sym < 64u)
         hipLaunchKernelGGL(jaro_word_asm_kernel<true>, g, b, 0, stream, q);
     else if (asm_ok)

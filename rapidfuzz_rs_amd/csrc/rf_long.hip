@@ -276,7 +276,7 @@ static hipError_t launch_wf_reg(const ScanParams& p, hipStream_t stream)
 
 hipError_t launch_wf(const ScanParams& p, hipStream_t stream)
 {
-    static const bool use_reg = [] { const char* e = getenv("RF_WF_REG"); return !e || atoi(e) != 0; }();  // A/B switch
+    static const bool use_reg = env_on("RF_WF_REG");  // A/B switch
     if (use_reg && p.len1 <= 16) return launch_wf_reg<16>(p, stream);
     if (use_reg && p.len1 <= 32) return launch_wf_reg<32>(p, stream);
     if (use_reg && p.len1 <= 64) return launch_wf_reg<64>(p, stream);

@@ -200,7 +200,7 @@ __global__ __launch_bounds__(256) void translate_direct_kernel(const Sym* __rest
 template <class Sym>
 static hipError_t launch_translate_t(const Sym* raw, uint64_t n_chunks, const uint32_t* keys, const uint8_t* vals, uint32_t cap, uint4* out, hipStream_t stream)
 {
-    static const bool direct = [] { const char* e = getenv("RF_TRANSLATE_DIRECT"); return !e || atoi(e) != 0; }();  // A/B switch
+    static const bool direct = env_on("RF_TRANSLATE_DIRECT");  // A/B switch
     if (direct && n_chunks >= 1024) {  // (below that the table set-up -- 64 KiB per workgroup -- is the larger part)
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(translate_direct_kernel<Sym>), hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
         if (e != hipSuccess) return e;
@@ -284,8 +284,8 @@ __global__ __launch_bounds__(256) void gather_results_kernel(const T* __restrict
 hipError_t launch_gather_results(const void* tmp, const uint32_t* slot_of, void* out, uint32_t n, bool f64, hipStream_t stream)
 {
     if (n == 0) return hipSuccess;
-    static const uint32_t span = [] { const char* e = getenv("RF_GATHER_SPAN"); return e ? (uint32_t)atoi(e) : 16384u; }();  // tuning knobs
-    static const int unroll = [] { const char* e = getenv("RF_GATHER_UNROLL"); return e ? atoi(e) : 8; }();
+    static const uint32_t span = (uint32_t)env_int("RF_GATHER_SPAN", 16384);  // tuning knobs
+    static const int unroll = (int)env_int("RF_GATHER_UNROLL", 8);
     const dim3 g(std::min<uint32_t>((n + span - 1) / span, (uint32_t)scan_max_grid())), b(256);
     if (f64)
         hipLaunchKernelGGL((gather_results_kernel<double, 8>), g, b, 0, stream, static_cast<const double*>(tmp), slot_of, static_cast<double*>(out), n, span);
@@ -448,7 +448,7 @@ hipError_t launch_window_gather(const void* tmp, const uint32_t* orig, const uin
     // (measured, 100 M u32 results of 64 lengths, whole Indel step: 2 windows x 8 runs in flight 1.125 ms; 2 x 4: 1.155; 4 x 4: 1.19;
     // 4 x 8: 1.15; 1 x 4: 1.165; 2 x 16: 1.15; 1 x 8: 1.185 -- gather_results_kernel: 1.226)
     const uint32_t span = (f64 ? 1u : 2u) * kGatherWindow;
-    static const bool use_deal = [] { const char* e = getenv("RF_GATHER_XCD"); return !e || atoi(e) != 0; }();
+    static const bool use_deal = env_on("RF_GATHER_XCD");
     uint32_t grid = std::min<uint32_t>((n + span - 1) / span, (uint32_t)scan_max_grid());
     const uint32_t deal = (use_deal && grid >= 64) ? 1u : 0u;
     if (deal) grid = (grid + 7) / 8 * 8;

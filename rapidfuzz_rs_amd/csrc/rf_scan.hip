@@ -207,7 +207,7 @@ __device__ __forceinline__ uint32_t band_hits(const uint8_t* lds_band, uint32_t 
 // leaves the filter nothing to decide): the 32-bit recurrence over the first kFirst columns of BOTH candidates of a lane (two
 // independent chains) and the diagonal bound.  Inside early_head8_kernel that look sits in a loop of 25 scalar instructions and
 // 12 branches per tile, one tile per trip.
-// buf: [0] packed count | G per-wavefront counts | G words unused | G segments of `cap` tiles | the packed list   (G = wavefronts of this launch)
+// buf: ListLayout (rf_list_layout.hpp), tiles form or -- kLanes -- lanes form; G = wavefronts of this launch
 // kPlane6: the pass reads the 6-bit plane (ScanParams::heads6: three coalesced dword loads per lane and pair, 768 B per wavefront instead
 // of 1024) and widens the two candidates to the byte form of the 8-byte plane in registers -- ~30 more vector instructions per pair in a
 // pass that is bound by the stream (C5 shape, 100 M candidates: 138 -> ~105 us).
@@ -236,8 +236,8 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void head_filter_kernel(cons
     const uint32_t wave = uniform(threadIdx.x / kWave);
     const uint32_t pairs = (p.tile_end - p.tile_begin + 1) / 2, stride = gridDim.x * kWavesPerBlock;
     const uint32_t gw = blockIdx.x * kWavesPerBlock + wave;
-    // kLanes: [0] packed count | [1] survivors | 2 pad | G (tile count, lane count) pairs | G segments of `cap` 16-byte entries | the packed entries
-    uint32_t* seg = kLanes ? buf + 4 + 2 * (size_t)stride + (size_t)gw * cap * 4 : buf + 1 + 2 * (size_t)stride + (size_t)gw * cap;
+    const ListLayout L = ListLayout::of_launch(kLanes ? ListLayout::kLanes : ListLayout::kTiles, stride, cap);  // this wavefront's own segment, and its counts
+    uint32_t* seg = kLanes ? buf + L.segment_at(gw) : L.segment(buf, gw);  // (the same place; each form in the steps that leave its code as it was)
     uint32_t kept = 0, kept_lanes = 0;
     uint32_t pr = gw;
     if (pr < pairs) {
@@ -374,9 +374,9 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void head_filter_kernel(cons
     }
     if (lane == 0) {
         if constexpr (kLanes) {
-            reinterpret_cast<uint2*>(buf + 4)[gw] = make_uint2(kept, kept_lanes);  // (one 8-byte word per wavefront: the pack kernel adds them up in front of every block)
+            reinterpret_cast<uint2*>(buf + L.wave_counts_at())[gw] = make_uint2(kept, kept_lanes);  // (one 8-byte word per wavefront: the pack kernel adds them up in front of every block)
         } else {
-            buf[1 + gw] = kept;
+            buf[L.wave_counts_at() + gw] = kept;
         }
     }
 }
@@ -386,17 +386,18 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void head_filter_kernel(cons
 // copies its segments behind one another; the last workgroup leaves the total in buf[0].  (First version: one workgroup doing
 // everything, every thread walking 16 segments one dependent load after another: 123 us.  Second: an offsets kernel whose threads
 // read 16 CONSECUTIVE counts each -- 64-byte lane stride, 17 us through one CU's L1 -- and a copy kernel, 6 us.)
-// buf: [0] packed count | G per-wavefront counts | G words unused | G segments of `cap` tiles | the packed list
+// buf: ListLayout, tiles form
 __global__ __launch_bounds__(256) void tile_list_pack_kernel(uint32_t* __restrict__ buf, uint32_t G, uint32_t cap)
 {
     constexpr uint32_t kWaves = 256 / kWave;
     __shared__ uint32_t own[kWaves], front[kWaves];
     const uint32_t lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
     const uint32_t first = blockIdx.x * 256, s = first + threadIdx.x;
+    const ListLayout L = ListLayout::of_launch(ListLayout::kTiles, G, cap);
     uint32_t before = 0;  // this thread's share of the counts in front of the block
 #pragma unroll 8
-    for (uint32_t k = threadIdx.x; k < first; k += 256) before += buf[1 + k];
-    const uint32_t n = s < G ? buf[1 + s] : 0u;
+    for (uint32_t k = threadIdx.x; k < first; k += 256) before += buf[L.wave_counts_at() + k];
+    const uint32_t n = s < G ? buf[L.wave_counts_at() + s] : 0u;
     uint32_t incl = n;  // inclusive scan of n inside the wavefront
 #pragma unroll
     for (uint32_t d = 1; d < (uint32_t)kWave; d <<= 1) {
@@ -417,25 +418,26 @@ __global__ __launch_bounds__(256) void tile_list_pack_kernel(uint32_t* __restric
     }
     at += in_front;
     if (s < G) {
-        const uint32_t* seg = buf + 1 + 2 * (size_t)G + (size_t)s * cap;
-        uint32_t* packed = buf + 1 + 2 * (size_t)G + (size_t)G * cap;
+        const uint32_t* seg = buf + L.segment_at(s);
+        uint32_t* packed = buf + L.packed_at();
         for (uint32_t j = 0; j < n; ++j) packed[at + j] = seg[j];
     }
-    if (first + 256 >= G && threadIdx.x == 0) buf[0] = in_front + block_total;
+    if (first + 256 >= G && threadIdx.x == 0) buf[L.count_at()] = in_front + block_total;
 }
 
 // The same for the LANE lists of head_filter_kernel<..., kLanes = true> (round 6): 16-byte entries (tile, lane mask lo / hi, -), two counts per segment -- tiles and
 // surviving lanes -- and two running sums: an entry's last word becomes the number of survivors in front of it, which is what rf_sparse.hip searches.
 // first[j] = the packed entry that holds survivor 64 j: where dense tile j of the second pass starts looking (every entry holds >= 1 survivor, so the 64 entries
 // from there on hold all of the tile's 64).
-// buf: [0] packed entries | [1] survivors | 2 pad | G (tile count, lane count) pairs | G segments of `cap` entries | the packed entries | first[]
+// buf: ListLayout, lanes form; first_of: its first[]
 __global__ __launch_bounds__(256) void lane_list_pack_kernel(uint32_t* __restrict__ buf, uint32_t G, uint32_t cap, uint32_t* __restrict__ first_of)
 {
     constexpr uint32_t kWaves = 256 / kWave;
     __shared__ uint32_t own[kWaves], front[kWaves], own_l[kWaves], front_l[kWaves];
     const uint32_t lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
     const uint32_t first = blockIdx.x * 256, s = first + threadIdx.x;
-    const uint2* __restrict__ counts = reinterpret_cast<const uint2*>(buf + 4);  // (tiles, surviving lanes) per segment
+    const ListLayout L = ListLayout::of_launch(ListLayout::kLanes, G, cap);
+    const uint2* __restrict__ counts = reinterpret_cast<const uint2*>(buf + L.wave_counts_at());  // (tiles, surviving lanes) per segment
     uint32_t before = 0, before_l = 0;  // this thread's share of the counts in front of the block
 #pragma unroll 8
     for (uint32_t k = threadIdx.x; k < first; k += 256) {  // (independent loads, eight in flight: the last block's chain is what the kernel takes)
@@ -473,8 +475,8 @@ __global__ __launch_bounds__(256) void lane_list_pack_kernel(uint32_t* __restric
     // the copy: a thread per segment, FOUR entries' loads in flight at a time (one dependent 16-byte load and store per entry was the longest kernel of the step at
     // 5 % prefix sharers, ~90 entries per segment; a wavefront per segment was tried and is no faster: it walks its 64 segments one memory round trip after another)
     if (s < G) {
-        const uint4* seg = reinterpret_cast<const uint4*>(buf + 4 + 2 * (size_t)G) + (size_t)s * cap;
-        uint4* packed = reinterpret_cast<uint4*>(buf + 4 + 2 * (size_t)G) + (size_t)G * cap;
+        const uint4* seg = reinterpret_cast<const uint4*>(L.segment(buf, s));
+        uint4* packed = reinterpret_cast<uint4*>(L.segment(buf, G));  // (= buf + L.packed_at())
         uint32_t run = lat;
         auto place = [&](uint4 e, uint32_t j) {
             e.w = run;
@@ -491,8 +493,8 @@ __global__ __launch_bounds__(256) void lane_list_pack_kernel(uint32_t* __restric
         for (; j < n; ++j) place(seg[j], j);
     }
     if (first + 256 >= G && threadIdx.x == 0) {
-        buf[0] = in_front + block_total;
-        buf[1] = in_front_l + block_total_l;
+        buf[L.count_at()] = in_front + block_total;
+        buf[ListLayout::kLaneSurvivorsAt] = in_front_l + block_total_l;
     }
 }
 
@@ -970,29 +972,19 @@ static int device_cus()
     }
     return n;
 }
-static int env_or(const char* name, int dflt)
-{
-    const char* e = getenv(name);
-    const int v = e ? atoi(e) : 0;
-    return v > 0 ? v : dflt;
-}
+static int positive_or(long long v, int dflt) { return v > 0 ? (int)v : dflt; }  // (RF_SCAN_*: <= 0 means the default)
 int scan_max_grid()
 {
-    static const int per_cu = env_or("RF_SCAN_BLOCKS_PER_CU", 32);
+    static const int per_cu = positive_or(env_int("RF_SCAN_BLOCKS_PER_CU", 0), 32);
     return device_cus() * per_cu;
 }
 int scan_max_grid_full()
 {
-    static const int per_cu = env_or("RF_SCAN_BLOCKS_PER_CU_FULL", 256);
+    static const int per_cu = positive_or(env_int("RF_SCAN_BLOCKS_PER_CU_FULL", 0), 256);
     return device_cus() * per_cu;
 }
 
-// the A/B switches of the cutoff scans (read once per process)
-static bool env_on(const char* name)
-{
-    const char* e = getenv(name);
-    return !e || atoi(e) != 0;
-}
+// the A/B switches of the cutoff scans
 static bool sw_early_static() { static const bool v = env_on("RF_EARLY_STATIC"); return v; }
 static bool sw_early_lean() { static const bool v = env_on("RF_EARLY_LEAN"); return v; }          // early_lean_kernel
 static bool sw_narrow_look() { static const bool v = env_on("RF_NARROW_LOOK"); return v; }        // the 32-bit first look of early_lean_kernel
@@ -1000,23 +992,113 @@ static bool sw_head_two_pass() { static const bool v = env_on("RF_HEAD_TWO_PASS"
 static bool sw_head_look_pass() { static const bool v = env_on("RF_HEAD_LOOK_PASS"); return v; }  // ... also where the band filter does not apply
 static bool sw_lane_compact() { static const bool v = env_on("RF_LANE_COMPACT"); return v; }      // the second pass over surviving LANES (rf_sparse.hip) instead of surviving tiles
 
-// Will launch_scan run this launch as head_filter_kernel + a second pass?  (The conditions of RF_EARLY_CASE below, for callers that must know before they
-// launch: rf_filter_* hands the second pass a compact result instead of a dense vector.)
-bool head_two_pass_applies(RawKind raw, const ScanParams& p)
+// The listing pass of the two-pass roads: a wavefront per PAIR of tiles, at most 16 workgroups per CU and 4096 in all, so that its G wavefronts stay within
+// ListLayout::kMaxSegments whatever the device.
+static ListLayout head_list_layout(const ScanParams& p, ListLayout::Kind kind)
 {
-    if ((raw != RAW_LEV && raw != RAW_OSA) || p.words != 1 || !p.early || p.band || p.long_words_pad || p.tile_step != 1) return false;
-    if (p.mixed && p.mixed_end > p.mixed_begin) return false;
-    if (!sw_early_static() || !sw_early_lean() || p.tiles || p.uniform_len < (uint32_t)kChunk || !p.heads8) return false;
-    if (p.first_check < 4 || p.first_check > 8 || (p.first_check & 1u)) return false;
+    const uint32_t pairs = (p.tile_end - p.tile_begin + 1) / 2;
+    const uint32_t fgrid = std::min<uint32_t>((pairs + kWavesPerBlock - 1) / kWavesPerBlock, std::min<uint32_t>((uint32_t)device_cus() * 16u, 4096u));
+    return ListLayout::head(kind, pairs, fgrid * kWavesPerBlock);
+}
+
+// The single-word states get the look's column (and `early` itself) as compile-time facts: the run-time dispatch and flags cost the short per-tile loop of a cutoff
+// scan 83 scalar instructions and 34 branches per tile -- with four SIMDs sharing one scalar unit about as much time as its 139 vector instructions (cutoff 3:
+// 217 -> 237 Gpairs/s, top-16 237 -> 263).  RF_EARLY_STATIC=0 selects the run-time form for A/B.
+EarlyRoad early_road(RawKind raw, const ScanParams& p)
+{
+    const uint32_t J = p.first_check;
+    if (!sw_early_static() || J < 4 || J > 16 || (J & 1u)) return EarlyRoad::RunTime;
+    if (p.tiles) return EarlyRoad::Tiles;
+    if (!sw_early_lean() || p.uniform_len < (uint32_t)kChunk) return EarlyRoad::Uniform;
+    // the head plane: Levenshtein / OSA, a look within the plane's 8 columns, and (for the 64-bit states, whose look runs on 32-bit words) the diagonal through
+    // (len1, len2) crossing that column inside the first 32 rows
     const bool lev32 = raw == RAW_LEV && p.len1 <= 32;
-    const int32_t look_row = (int32_t)p.first_check + (int32_t)p.len1 - (int32_t)p.uniform_len;
-    if (!lev32 && (look_row < 1 || look_row > 32)) return false;
-    if (!(p.head_need ? sw_head_two_pass() : sw_head_look_pass())) return false;
-    return p.tile_list_buf != nullptr && p.tile_end > p.tile_begin;
+    const int32_t look_row = (int32_t)J + (int32_t)p.len1 - (int32_t)p.uniform_len;
+    if ((raw != RAW_LEV && raw != RAW_OSA) || J > 8 || !p.heads8 || !(lev32 || (look_row >= 1 && look_row <= 32))) return EarlyRoad::Lean;
+    // band prefilter and first look as a streaming pass of its own, then the cutoff scan over what it left: full scans with a list buffer that holds the pass' lists
+    if (!(p.head_need ? sw_head_two_pass() : sw_head_look_pass()) || p.tile_step != 1 || !p.tile_list_buf || p.tile_end <= p.tile_begin) return EarlyRoad::Head8;
+    const bool lanes = p.lane_list && sw_lane_compact();
+    if (!head_list_layout(p, lanes ? ListLayout::kLanes : ListLayout::kTiles).fits(p.tile_list_words)) return EarlyRoad::Head8;
+    return lanes ? EarlyRoad::TwoPassLanes : EarlyRoad::TwoPassTiles;
+}
+
+// pn: p with the launcher's own switches (narrow_look, exp_flags) filled in
+template <class State, int J>
+static hipError_t launch_early(EarlyRoad road, const ScanParams& p, const ScanParams& pn, hipStream_t stream, dim3 g)
+{
+    const dim3 b(kWave * kWavesPerBlock);
+    constexpr bool kHeadState = J <= 8 && (std::is_same<State, LevState<1>>::value || std::is_same<State, Lev32State>::value || std::is_same<State, OsaState<1>>::value);
+    if (road == EarlyRoad::Tiles) {
+        hipLaunchKernelGGL((early_kernel<State, false, J>), g, b, 0, stream, p);
+    } else if (road == EarlyRoad::Uniform) {
+        hipLaunchKernelGGL((early_kernel<State, true, J>), g, b, 0, stream, p);
+    } else if (road == EarlyRoad::Lean) {
+        hipLaunchKernelGGL((early_lean_kernel<State, J>), g, b, 0, stream, pn);
+    } else if constexpr (kHeadState) {
+        if (road == EarlyRoad::Head8) {
+            hipLaunchKernelGGL((early_head8_kernel<State, J>), g, b, 0, stream, pn);
+            return hipGetLastError();
+        }
+        const bool lanes = road == EarlyRoad::TwoPassLanes;
+        const ListLayout L = head_list_layout(p, lanes ? ListLayout::kLanes : ListLayout::kTiles);
+        const dim3 fg(L.G / kWavesPerBlock), pg((L.G + 255) / 256);
+        const bool plane6 = pn.heads6 && (p.tile_begin & 1u) == 0;
+        uint32_t* const buf = p.tile_list_buf;
+        ScanParams p2 = pn;
+        p2.heads8 = nullptr;
+        p2.tile_list = buf + L.packed_at();
+        p2.tile_list_count = buf + L.count_at();
+        if (lanes) {
+            // round 6: the pass leaves LANE masks with its surviving tiles, the second pass walks the surviving lanes 64 to a wavefront (rf_sparse.hip)
+            if (plane6)
+                hipLaunchKernelGGL((head_filter_kernel<State, J, true, true>), fg, b, 0, stream, pn, buf, L.cap);
+            else
+                hipLaunchKernelGGL((head_filter_kernel<State, J, false, true>), fg, b, 0, stream, pn, buf, L.cap);
+            hipLaunchKernelGGL(lane_list_pack_kernel, pg, dim3(256), 0, stream, buf, L.G, L.cap, buf + L.first_at());
+            p2.lane_first = buf + L.first_at();
+            hipError_t el = hipGetLastError();
+            if (el == hipSuccess) el = launch_sparse_lean(std::is_same<State, Lev32State>::value ? 1 : (std::is_same<State, OsaState<1>>::value ? 2 : 0), p2, stream);
+            return el;
+        }
+        if (plane6)
+            hipLaunchKernelGGL((head_filter_kernel<State, J, true>), fg, b, 0, stream, pn, buf, L.cap);
+        else
+            hipLaunchKernelGGL((head_filter_kernel<State, J, false>), fg, b, 0, stream, pn, buf, L.cap);
+        hipLaunchKernelGGL(tile_list_pack_kernel, pg, dim3(256), 0, stream, buf, L.G, L.cap);
+        hipLaunchKernelGGL((early_lean_kernel<State, J>), dim3((uint32_t)device_cus() * 8u), b, 0, stream, p2);
+    } else {
+        return hipErrorInvalidValue;  // (early_road() sends no other state down the head-plane roads)
+    }
+    return hipGetLastError();
+}
+
+// A launch split around the (at most two) runs of zero-length tiles of its range: the asm scans have no column to run there, so `scan` takes the ranges between the
+// runs and `zeros` -- a compiled kernel -- fills the runs in.
+template <class Scan, class Zeros>
+static hipError_t launch_around_zero_runs(const ScanParams& p, Scan scan, Zeros zeros)
+{
+    uint32_t at = p.tile_begin;
+    for (int r = 0; r <= 2 && at < p.tile_end; ++r) {
+        const uint32_t zb = r < 2 ? std::min(std::max(p.zero_begin[r], at), p.tile_end) : p.tile_end;
+        const uint32_t ze = r < 2 ? std::min(std::max(p.zero_end[r], zb), p.tile_end) : p.tile_end;
+        if (r < 2 && p.zero_end[r] <= p.zero_begin[r]) continue;  // no such run
+        ScanParams q = p;
+        if (zb > at) {
+            q.tile_begin = at, q.tile_end = zb;
+            const hipError_t e = scan(q, std::max(1, scan_grid_full(zb - at)));
+            if (e != hipSuccess) return e;
+        }
+        if (ze > zb) {
+            q.tile_begin = zb, q.tile_end = ze;
+            zeros(q, dim3(std::max(1, scan_grid(ze - zb))));
+        }
+        at = ze;
+    }
+    return hipGetLastError();
 }
 
 template <class State>
-static hipError_t launch_state(const ScanParams& p, hipStream_t stream, int grid)
+static hipError_t launch_state(RawKind raw, const ScanParams& p, hipStream_t stream, int grid)
 {
     const dim3 g(grid), b(kWave * kWavesPerBlock);
     if constexpr (State::kWords == 1) {
@@ -1024,14 +1106,14 @@ static hipError_t launch_state(const ScanParams& p, hipStream_t stream, int grid
         // 1-3 % slower), 2 for the LCS states, whose 5-instruction column makes a chunk short enough for a second load in flight to
         // pay (Indel 80.8 -> 81.6 Gpairs/s, depth 3: 79.6); RF_STREAM=0 selects scan_body for A/B.
         constexpr int kDepth = (std::is_same<State, LcsState<1>>::value || std::is_same<State, Lcs32State>::value) ? 2 : 1;
-        static const bool use_stream = [] { const char* e = getenv("RF_STREAM"); return !e || atoi(e) != 0; }();
+        static const bool use_stream = env_on("RF_STREAM");
         if (!p.early && use_stream) {
             // the headline case has its chunk in hand-scheduled asm (rf_lev_asm.hip); RF_ASM_CHUNK=0 selects the compiled loop
-            static const bool use_asm = [] { const char* e = getenv("RF_ASM_CHUNK"); return !e || atoi(e) != 0; }();
+            const bool use_asm = sw_asm_chunk();
             // per-candidate u32 results of the Levenshtein / OSA states: the whole-kernel asm scans (rf_stream_asm.hip), whatever the
             // corpus looks like.  Zero-length tiles have no column to run: the compiled loop fills those runs in.  RF_ASM_STREAM=0
             // keeps round 2's fixed-shape asm kernels + the compiled loop for A/B.
-            static const bool use_stream_asm = [] { const char* e = getenv("RF_ASM_STREAM"); return !e || atoi(e) != 0; }();
+            static const bool use_stream_asm = env_on("RF_ASM_STREAM");
             constexpr int kAsmKind = std::is_same<State, LevState<1>>::value ? 0 : (std::is_same<State, Lev32State>::value ? 1 : (std::is_same<State, OsaState<1>>::value ? 2 : -1));
             // the single-word LCS scans of a single-length corpus that keeps its payload at 6 bits per symbol too (ScanParams::data6): the asm scan over that
             // (whole chunks only: lengths that are multiples of 16; u32 results).  RF_PACK6=0 (no such payload) is the A/B switch.
@@ -1041,27 +1123,10 @@ static hipError_t launch_state(const ScanParams& p, hipStream_t stream, int grid
             // ... and the same scans over the 6-bit payload of a length-bucketed corpus (tiles; u32 results)
             constexpr bool kLcs1 = std::is_same<State, LcsState<1>>::value || std::is_same<State, Lcs32State>::value;
             const int asm_kind = kAsmKind >= 0 ? kAsmKind : ((kLcs1 && p.data6 && p.tiles) ? (std::is_same<State, Lcs32State>::value ? 6 : 5) : -1);
-            if (asm_kind >= 0 && use_asm && use_stream_asm && stream_asm_serves(p)) {
-                uint32_t at = p.tile_begin;
-                for (int r = 0; r <= 2 && at < p.tile_end; ++r) {
-                    const uint32_t zb = r < 2 ? std::min(std::max(p.zero_begin[r], at), p.tile_end) : p.tile_end;
-                    const uint32_t ze = r < 2 ? std::min(std::max(p.zero_end[r], zb), p.tile_end) : p.tile_end;
-                    if (r < 2 && p.zero_end[r] <= p.zero_begin[r]) continue;  // no such run
-                    if (zb > at) {
-                        ScanParams q = p;
-                        q.tile_begin = at, q.tile_end = zb;
-                        const hipError_t e = launch_stream_asm(asm_kind, q, stream, std::max(1, scan_grid_full(zb - at)));
-                        if (e != hipSuccess) return e;
-                    }
-                    if (ze > zb) {
-                        ScanParams q = p;
-                        q.tile_begin = zb, q.tile_end = ze;
-                        hipLaunchKernelGGL((stream_kernel_occ8<State, false, kDepth>), dim3(std::max(1, scan_grid(ze - zb))), b, 0, stream, q);
-                    }
-                    at = ze;
-                }
-                return hipGetLastError();
-            }
+            if (asm_kind >= 0 && use_asm && use_stream_asm && stream_asm_serves(p))
+                return launch_around_zero_runs(
+                    p, [&](const ScanParams& q, int qgrid) { return launch_stream_asm(asm_kind, q, stream, qgrid); },
+                    [&](const ScanParams& q, dim3 qg) { hipLaunchKernelGGL((stream_kernel_occ8<State, false, kDepth>), qg, b, 0, stream, q); });
             if (std::is_same<State, LevState<1>>::value && !p.tiles && use_asm && p.uniform_len >= (uint32_t)kChunk && p.uniform_len % kChunk == 0)
                 return launch_lev1_asm(p, stream, grid);
             if (std::is_same<State, Lev32State>::value && !p.tiles && use_asm && p.uniform_len >= (uint32_t)kChunk && p.uniform_len % kChunk == 0)
@@ -1078,87 +1143,24 @@ static hipError_t launch_state(const ScanParams& p, hipStream_t stream, int grid
             // cutoff runs: the compiler's own register budget.  Pinned to 8 wavefronts per SIMD this body spills (32 B of
             // scratch traffic per tile in a loop that only runs 8 columns); 7 resident wavefronts without spills
             // measured +8 % at cutoff 3 and +3 % at cutoff 10 on the C2 corpus.
-            // The single-word states get the look's column (and `early` itself) as compile-time facts: the run-time dispatch
-            // and flags cost the short per-tile loop of a cutoff scan 83 scalar instructions and 34 branches per tile -- with
-            // four SIMDs sharing one scalar unit about as much time as its 139 vector instructions (cutoff 3: 217 -> 237
-            // Gpairs/s, top-16 237 -> 263).  RF_EARLY_STATIC=0 selects the run-time form for A/B.
-            const bool early_static = sw_early_static(), lean = sw_early_lean(), narrow_look = sw_narrow_look();
             ScanParams pn = p;
-            pn.narrow_look = narrow_look ? 1u : 0u;
-            const bool two_pass = sw_head_two_pass(), look_pass = sw_head_look_pass();
-#ifdef RF_EXPERIMENTS  // measurement builds only (tools/build_stream_variant.sh): the shipping library has no switch that changes a result
-            static const bool exp_nohbm = getenv("RF_EXP_NOHBM") != nullptr;  // every tile reads tile 0's head row (results are wrong on purpose)
-            pn.exp_flags = exp_nohbm ? 1u : 0u;
+            pn.narrow_look = sw_narrow_look() ? 1u : 0u;
+#ifdef RF_EXPERIMENTS
+            pn.exp_flags = sw_exp_nohbm() ? 1u : 0u;  // (bit 0: every tile reads tile 0's head row)
 #else
             pn.exp_flags = 0u;
 #endif
-            if constexpr (std::is_same<State, LevState<1>>::value || std::is_same<State, Lev32State>::value || std::is_same<State, OsaState<1>>::value ||
-                          std::is_same<State, LcsState<1>>::value || std::is_same<State, Lcs32State>::value) {
-                if (early_static) {
-#define RF_EARLY_CASE(J)                                                                   \
-    case J:                                                                                \
-        if (p.tiles)                                                                       \
-            hipLaunchKernelGGL((early_kernel<State, false, J>), g, b, 0, stream, p);       \
-        else if (lean && p.uniform_len >= (uint32_t)kChunk) {                              \
-            if constexpr (J <= 8 && (std::is_same<State, LevState<1>>::value || std::is_same<State, Lev32State>::value || std::is_same<State, OsaState<1>>::value)) { \
-                const int32_t look_row = J + (int32_t)p.len1 - (int32_t)p.uniform_len;      \
-                if (p.heads8 && (std::is_same<State, Lev32State>::value || (look_row >= 1 && look_row <= 32))) { \
-                    if ((p.head_need ? two_pass : look_pass) && p.tile_step == 1 && p.tile_list_buf && p.tile_end > p.tile_begin) { \
-                        /* band prefilter and first look as a streaming pass of its own, then the cutoff scan over the tiles it left */ \
-                        const uint32_t pairs = (p.tile_end - p.tile_begin + 1) / 2;        \
-                        const uint32_t fgrid = std::min<uint32_t>((pairs + kWavesPerBlock - 1) / kWavesPerBlock, std::min<uint32_t>((uint32_t)device_cus() * 16u, 4096u)); /* G <= 16 K: rf_api_scan.hip sizes the list buffer for that */ \
-                        const uint32_t G = fgrid * kWavesPerBlock, cap = 2 * ((pairs + G - 1) / G); \
-                        if (pn.lane_list && sw_lane_compact()) {                          \
-                            /* round 6: the pass leaves LANE masks with its surviving tiles, the second pass walks the surviving lanes 64 to a wavefront (rf_sparse.hip) */ \
-                            const uint32_t cap4 = cap;                                     \
-                            if (pn.heads6 && (p.tile_begin & 1u) == 0)                     \
-                                hipLaunchKernelGGL((head_filter_kernel<State, J, true, true>), dim3(fgrid), b, 0, stream, pn, p.tile_list_buf, cap4); \
-                            else                                                           \
-                                hipLaunchKernelGGL((head_filter_kernel<State, J, false, true>), dim3(fgrid), b, 0, stream, pn, p.tile_list_buf, cap4); \
-                            uint32_t* packed_at = p.tile_list_buf + 4 + 2 * (size_t)G + 4 * (size_t)G * cap4; \
-                            uint32_t* first_at = packed_at + 4 * (size_t)(2 * pairs + 2);   \
-                            hipLaunchKernelGGL(lane_list_pack_kernel, dim3((G + 255) / 256), dim3(256), 0, stream, p.tile_list_buf, G, cap4, first_at); \
-                            ScanParams p2 = pn;                                            \
-                            p2.heads8 = nullptr;                                           \
-                            p2.tile_list = packed_at;                                      \
-                            p2.lane_first = first_at;                                      \
-                            p2.tile_list_count = p.tile_list_buf;                          \
-                            hipError_t el = hipGetLastError();                             \
-                            if (el == hipSuccess) el = launch_sparse_lean(std::is_same<State, Lev32State>::value ? 1 : (std::is_same<State, OsaState<1>>::value ? 2 : 0), p2, stream); \
-                            return el;                                                     \
-                        }                                                                  \
-                        if (pn.heads6 && (p.tile_begin & 1u) == 0)                         \
-                            hipLaunchKernelGGL((head_filter_kernel<State, J, true>), dim3(fgrid), b, 0, stream, pn, p.tile_list_buf, cap); \
-                        else                                                               \
-                            hipLaunchKernelGGL((head_filter_kernel<State, J, false>), dim3(fgrid), b, 0, stream, pn, p.tile_list_buf, cap); \
-                        hipLaunchKernelGGL(tile_list_pack_kernel, dim3((G + 255) / 256), dim3(256), 0, stream, p.tile_list_buf, G, cap); \
-                        ScanParams p2 = pn;                                                \
-                        p2.heads8 = nullptr;                                               \
-                        p2.tile_list = p.tile_list_buf + 1 + 2 * (size_t)G + (size_t)G * cap; \
-                        p2.tile_list_count = p.tile_list_buf;                              \
-                        hipLaunchKernelGGL((early_lean_kernel<State, J>), dim3((uint32_t)device_cus() * 8u), b, 0, stream, p2); \
-                        return hipGetLastError();                                          \
-                    }                                                                      \
-                    hipLaunchKernelGGL((early_head8_kernel<State, J>), g, b, 0, stream, pn); \
-                    return hipGetLastError();                                              \
-                }                                                                          \
-            }                                                                              \
-            hipLaunchKernelGGL((early_lean_kernel<State, J>), g, b, 0, stream, pn);        \
-        }                                                                                  \
-        else                                                                               \
-            hipLaunchKernelGGL((early_kernel<State, true, J>), g, b, 0, stream, p);        \
-        return hipGetLastError();
-                    switch (p.first_check) {
-                        RF_EARLY_CASE(4)
-                        RF_EARLY_CASE(6)
-                        RF_EARLY_CASE(8)
-                        RF_EARLY_CASE(10)
-                        RF_EARLY_CASE(12)
-                        RF_EARLY_CASE(14)
-                        RF_EARLY_CASE(16)
-                    default: break;
-                    }
-#undef RF_EARLY_CASE
+            const EarlyRoad road = early_road(raw, p);
+            if (road != EarlyRoad::RunTime) {
+                switch (p.first_check) {
+                case 4: return launch_early<State, 4>(road, p, pn, stream, g);
+                case 6: return launch_early<State, 6>(road, p, pn, stream, g);
+                case 8: return launch_early<State, 8>(road, p, pn, stream, g);
+                case 10: return launch_early<State, 10>(road, p, pn, stream, g);
+                case 12: return launch_early<State, 12>(road, p, pn, stream, g);
+                case 14: return launch_early<State, 14>(road, p, pn, stream, g);
+                case 16: return launch_early<State, 16>(road, p, pn, stream, g);
+                default: return hipErrorInvalidValue;  // (early_road() answers RunTime for every other column)
                 }
             }
             if (p.tiles)
@@ -1174,29 +1176,12 @@ static hipError_t launch_state(const ScanParams& p, hipStream_t stream, int grid
     } else {
         // queries of 65 .. 512 symbols, one u32 per candidate, no cutoff: the multi-word asm scans (rf_stream_asm.hip, word planes in
         // LDS); zero-length tiles go to the compiled kernel like above.  RF_ASM_BLOCK=0 keeps the compiled kernel for A/B.
-        static const bool use_block_asm = [] { const char* e = getenv("RF_ASM_BLOCK"); return !e || atoi(e) != 0; }();
+        static const bool use_block_asm = env_on("RF_ASM_BLOCK");
         constexpr bool kLevW = std::is_same<State, LevState<State::kWords>>::value && State::kWords >= 2 && State::kWords <= 8;  // (round 5: 5 .. 8 words too)
-        if (kLevW && use_block_asm && stream_asm_serves(p)) {
-            uint32_t at = p.tile_begin;
-            for (int r = 0; r <= 2 && at < p.tile_end; ++r) {
-                const uint32_t zb = r < 2 ? std::min(std::max(p.zero_begin[r], at), p.tile_end) : p.tile_end;
-                const uint32_t ze = r < 2 ? std::min(std::max(p.zero_end[r], zb), p.tile_end) : p.tile_end;
-                if (r < 2 && p.zero_end[r] <= p.zero_begin[r]) continue;  // no such run
-                if (zb > at) {
-                    ScanParams q = p;
-                    q.tile_begin = at, q.tile_end = zb;
-                    const hipError_t e = launch_stream_asm(3, q, stream, std::max(1, scan_grid_full(zb - at)));
-                    if (e != hipSuccess) return e;
-                }
-                if (ze > zb) {
-                    ScanParams q = p;
-                    q.tile_begin = zb, q.tile_end = ze;
-                    hipLaunchKernelGGL((scan_kernel<State, false>), dim3(std::max(1, scan_grid(ze - zb))), b, 0, stream, q);
-                }
-                at = ze;
-            }
-            return hipGetLastError();
-        }
+        if (kLevW && use_block_asm && stream_asm_serves(p))
+            return launch_around_zero_runs(
+                p, [&](const ScanParams& q, int qgrid) { return launch_stream_asm(3, q, stream, qgrid); },
+                [&](const ScanParams& q, dim3 qg) { hipLaunchKernelGGL((scan_kernel<State, false>), qg, b, 0, stream, q); });
         if (p.tiles)
             hipLaunchKernelGGL((scan_kernel<State, false>), g, b, 0, stream, p);
         else
@@ -1206,17 +1191,17 @@ static hipError_t launch_state(const ScanParams& p, hipStream_t stream, int grid
 }
 
 template <template <int> class StateT>
-static hipError_t launch_words(const ScanParams& p, hipStream_t stream, int grid)
+static hipError_t launch_words(RawKind raw, const ScanParams& p, hipStream_t stream, int grid)
 {
     switch (p.words) {
-    case 1: return launch_state<StateT<1>>(p, stream, grid);
-    case 2: return launch_state<StateT<2>>(p, stream, grid);
-    case 3: return launch_state<StateT<3>>(p, stream, grid);
-    case 4: return launch_state<StateT<4>>(p, stream, grid);
-    case 5: return launch_state<StateT<5>>(p, stream, grid);
-    case 6: return launch_state<StateT<6>>(p, stream, grid);
-    case 7: return launch_state<StateT<7>>(p, stream, grid);
-    case 8: return launch_state<StateT<8>>(p, stream, grid);
+    case 1: return launch_state<StateT<1>>(raw, p, stream, grid);
+    case 2: return launch_state<StateT<2>>(raw, p, stream, grid);
+    case 3: return launch_state<StateT<3>>(raw, p, stream, grid);
+    case 4: return launch_state<StateT<4>>(raw, p, stream, grid);
+    case 5: return launch_state<StateT<5>>(raw, p, stream, grid);
+    case 6: return launch_state<StateT<6>>(raw, p, stream, grid);
+    case 7: return launch_state<StateT<7>>(raw, p, stream, grid);
+    case 8: return launch_state<StateT<8>>(raw, p, stream, grid);
     default: return hipErrorInvalidValue;
     }
 }
@@ -1236,7 +1221,7 @@ int scan_grid(uint32_t n_tiles)
 // RF_SCAN_BLOCKS_PER_CU_FULL (256) per CU, a multiple of 8 (the XCD deal).  profiles/grid_sweep_r04.txt
 int scan_grid_full(uint32_t n_tiles)
 {
-    static const uint32_t per_wave = (uint32_t)env_or("RF_SCAN_TILES_PER_WAVE", 5);
+    static const uint32_t per_wave = (uint32_t)positive_or(env_int("RF_SCAN_TILES_PER_WAVE", 0), 5);
     const uint32_t by_tiles = (n_tiles + kWavesPerBlock - 1) / kWavesPerBlock;  // one tile per wavefront
     const uint32_t want = (n_tiles + kWavesPerBlock * per_wave - 1) / (kWavesPerBlock * per_wave);
     const uint32_t fill = std::min<uint32_t>(by_tiles, (uint32_t)device_cus() * 32u);  // (below ~10 M candidates: as many workgroups as there are)
@@ -1250,7 +1235,7 @@ hipError_t launch_scan(RawKind raw, const ScanParams& p_in, hipStream_t stream, 
 #ifdef RF_EXPERIMENTS  // measurement builds only: RF_EXP_TILE_BYTES=<bytes> walks a single-length corpus at another tile pitch (results are wrong on purpose:
                        // what would a scan gain if its payload were that much smaller, with its arithmetic unchanged?)
     ScanParams p_exp = p_in;
-    static const uint32_t exp_tile_bytes = [] { const char* e = getenv("RF_EXP_TILE_BYTES"); return e ? (uint32_t)atoi(e) : 0u; }();
+    static const uint32_t exp_tile_bytes = (uint32_t)env_int("RF_EXP_TILE_BYTES", 0);
     if (exp_tile_bytes && !p_exp.tiles) p_exp.uniform_tile_bytes = exp_tile_bytes;
     const ScanParams& p = p_exp;
 #else
@@ -1269,7 +1254,7 @@ hipError_t launch_scan(RawKind raw, const ScanParams& p_in, hipStream_t stream, 
         // A small corpus costs two launches and the gap between them: up to RF_JOINT_MAX_TILES exact tiles the mixed kernel walks them
         // too, as tiles whose 64 lanes share one length.  configs[0] (query 32 x 10 k candidates): 12.5 -> 6.9 us per call; 500 k
         // candidates 18.0 -> 11.2; 1 M 30 -> 22; 2 M 38.6 -> 38.1 (beyond that the asm kernels' rate wins): profiles/joint_launch_r04.txt
-        static const uint32_t joint_max = [] { const char* e = getenv("RF_JOINT_MAX_TILES"); return e ? (uint32_t)atoi(e) : 16384u; }();
+        static const uint32_t joint_max = (uint32_t)env_int("RF_JOINT_MAX_TILES", 16384);
         if (!p.prefill_none && p.tiles && p.orig && !p.run_orig && q.tile_end - q.tile_begin <= joint_max) {
             ScanParams m = p;
             m.joint_begin = q.tile_begin;
@@ -1303,9 +1288,9 @@ hipError_t launch_scan(RawKind raw, const ScanParams& p_in, hipStream_t stream, 
     if (p.band && raw == RAW_LEV && !p.topk_k) return launch_band(p, stream);
     if (p.long_words_pad && (raw == RAW_LEV || raw == RAW_LCS || raw == RAW_OSA)) return launch_long(raw, p, stream, grid);
     switch (raw) {
-    case RAW_LEV: return p.len1 <= 32 ? launch_state<Lev32State>(p, stream, grid) : launch_words<LevState>(p, stream, grid);
-    case RAW_LCS: return p.len1 <= 32 ? launch_state<Lcs32State>(p, stream, grid) : launch_words<LcsState>(p, stream, grid);
-    case RAW_OSA: return launch_words<OsaState>(p, stream, grid);
+    case RAW_LEV: return p.len1 <= 32 ? launch_state<Lev32State>(raw, p, stream, grid) : launch_words<LevState>(raw, p, stream, grid);
+    case RAW_LCS: return p.len1 <= 32 ? launch_state<Lcs32State>(raw, p, stream, grid) : launch_words<LcsState>(raw, p, stream, grid);
+    case RAW_OSA: return launch_words<OsaState>(raw, p, stream, grid);
     case RAW_WF: return launch_wf(p, stream);
     case RAW_JARO: return launch_jaro(p, stream);
     default: return hipErrorInvalidValue;

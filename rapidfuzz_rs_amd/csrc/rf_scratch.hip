@@ -34,10 +34,7 @@ struct Pool {
     std::map<void*, Block> in_use;
     std::vector<Block> parked;
     size_t parked_bytes = 0;
-    size_t cap = [] {
-        const char* e = getenv("RF_SCRATCH_CACHE_MB");
-        return (size_t)(e ? std::max(0ll, atoll(e)) : 1024ll) << 20;
-    }();
+    size_t cap = (size_t)std::max(0ll, env_int("RF_SCRATCH_CACHE_MB", 1024)) << 20;
 };
 
 Pool& pool()

@@ -36,7 +36,7 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void sparse_lean_kernel(cons
     __shared__ typename State::Word lds_pm[256];
     __shared__ uint64_t lds_topk[kWavesPerBlock][kWave];
     const uint4* __restrict__ list = reinterpret_cast<const uint4*>(p.tile_list);  // (tile, lane mask lo, hi, survivors in front): lane_list_pack_kernel
-    const uint32_t entries = uniform(p.tile_list_count[0]), total = uniform(p.tile_list_count[1]);
+    const uint32_t entries = uniform(p.tile_list_count[0]), total = uniform(p.tile_list_count[ListLayout::kLaneSurvivorsAt]);
     const uint32_t n_dense = (total + kWave - 1) / kWave;
     const bool topk = p.topk_k != 0;
     // (the survivors' number is only known here: the grid is sized for many, and a workgroup without a dense tile leaves before it stages the table -- unless the
@@ -168,7 +168,7 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void sparse_words_kernel(con
     constexpr int W = State::kWords;
     __shared__ typename State::Word lds_pm[256 * W];
     const uint4* __restrict__ list = reinterpret_cast<const uint4*>(p.tile_list);
-    const uint32_t entries = uniform(p.tile_list_count[0]), total = uniform(p.tile_list_count[1]);
+    const uint32_t entries = uniform(p.tile_list_count[0]), total = uniform(p.tile_list_count[ListLayout::kLaneSurvivorsAt]);
     const uint32_t n_dense = (total + kWave - 1) / kWave;
     if (blockIdx.x == 0 && threadIdx.x == 0 && p.band_report) {  // what the first pass left, for the host's bookkeeping of the hint (read there without waiting)
         __hip_atomic_store(p.band_report + 8, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);

@@ -61,3 +61,33 @@ def test_stream_asm_include_is_the_generators_output(tmp_path):
     struct = hip[hip.index("struct StreamAsmArgs {"): hip.index("};", hip.index("struct StreamAsmArgs {"))]
     for name in re.findall(r"#define RF_STREAM_ARG_(\w+) \d+", out.read_text()):
         assert re.search(rf"\b{name.lower()}\b", struct.lower()), name
+
+
+def test_environment_table_names_every_switch_the_library_reads():
+    """include/rfgpu.h documents the RF_* environment variables; the sources read them through the three helpers of rf_internal.hpp (env_on / env_set /
+    env_int) and nothing else.  The two sets must be equal; the RF_EXP_* switches, compiled into -DRF_EXPERIMENTS builds only, are named in the header's
+    prose and compared on their own."""
+    import glob
+    import re
+
+    csrc = os.path.join(ROOT, "rapidfuzz_rs_amd", "csrc")
+    read, stray = set(), []
+    for path in sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.hpp")) + glob.glob(os.path.join(csrc, "*.inc"))):
+        text = open(path, errors="replace").read()
+        read |= set(re.findall(r"\benv_(?:on|set|int)\(\s*\"(RF_[A-Z0-9_]+)\"", text))
+        if os.path.basename(path) != "rf_internal.hpp" and re.search(r"\bgetenv\s*\(", text):
+            stray.append(os.path.basename(path))
+    assert not stray, f"getenv() outside the helpers of rf_internal.hpp: {stray}"
+    header = open(os.path.join(ROOT, "include", "rfgpu.h")).read()
+    comment = header[:header.index("#ifndef RFGPU_H")]
+    table = comment[comment.index("name                          default   meaning"):]
+    documented = set()
+    for line in table.splitlines():
+        m = re.match(r" \*   ((?:RF_[A-Z0-9_]+(?: / )?)+)", line)  # a row starts with its name(s); continuation lines are indented further
+        if m:
+            documented |= set(re.findall(r"RF_[A-Z0-9_]+", m.group(1)))
+    exp_read = {n for n in read if n.startswith("RF_EXP_")}
+    exp_documented = set(re.findall(r"RF_EXP_[A-Z0-9_]+", comment))
+    assert len(documented) >= 50, sorted(documented)  # (the parser found the table)
+    assert read - exp_read == documented, sorted((read - exp_read) ^ documented)
+    assert exp_read == exp_documented, sorted(exp_read ^ exp_documented)
