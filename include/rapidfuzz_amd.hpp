@@ -1,5 +1,5 @@
 // rapidfuzz_amd.hpp -- header-only C++17 facade over the C ABI of rfgpu.h that mirrors the reference's names:
-//   rapidfuzz::distance::{levenshtein, indel, lcs_seq, jaro, jaro_winkler}::{Args, BatchComparator, distance, ...}
+//   rapidfuzz::distance::{levenshtein, indel, lcs_seq, damerau_levenshtein, jaro, jaro_winkler}::{Args, BatchComparator, distance, ...}
 //   rapidfuzz::fuzz::{ratio, RatioBatchComparator}
 // `Option<T>` becomes std::optional<T>; the one-vs-many entry points take a rapidfuzz::Corpus.
 // Reference: rapidfuzz-rs v0.5.0, e.g. src/distance/levenshtein.rs:86-148 (Args, WeightTable), :1636-1818
@@ -280,6 +280,7 @@ namespace distance {
 using levenshtein = detail::Module<RF_LEVENSHTEIN, false>;    // src/distance/levenshtein.rs
 using indel = detail::Module<RF_INDEL, false>;                // src/distance/indel.rs
 using lcs_seq = detail::Module<RF_LCS_SEQ, false>;            // src/distance/lcs_seq.rs
+using damerau_levenshtein = detail::Module<RF_DAMERAU_LEVENSHTEIN, false>;  // src/distance/damerau_levenshtein.rs
 using jaro = detail::Module<RF_JARO, true>;                   // src/distance/jaro.rs
 using jaro_winkler = detail::Module<RF_JARO_WINKLER, true>;   // src/distance/jaro_winkler.rs
 }  // namespace distance

@@ -125,7 +125,9 @@ typedef enum rf_metric {
     RF_JARO = 3,         /* src/distance/jaro.rs */
     RF_JARO_WINKLER = 4, /* src/distance/jaro_winkler.rs */
     RF_FUZZ_RATIO = 5,   /* src/fuzz.rs RatioBatchComparator */
-    RF_OSA = 6           /* src/distance/osa.rs (widening beyond the north-star path) */
+    RF_OSA = 6,          /* src/distance/osa.rs (widening beyond the north-star path) */
+    RF_DAMERAU_LEVENSHTEIN = 7 /* src/distance/damerau_levenshtein.rs:191-215 (the unrestricted distance, distance_zhao :111-168; no bit-parallel path in the
+                                  reference either: a row DP per candidate, rf_damerau.hip) */
 } rf_metric;
 
 /* the four methods every BatchComparator has (e.g. levenshtein.rs:1660-1817) */
@@ -145,7 +147,7 @@ typedef enum rf_mem { RF_MEM_HOST = 0, RF_MEM_DEVICE = 1 } rf_mem;
 /*
  * Flattened `Args` builders: levenshtein.rs:86-126 (score_cutoff, score_hint, weights),
  * jaro_winkler.rs:25-62 (prefix_weight), and the identical score_cutoff/score_hint pairs of
- * lcs_seq / indel / jaro / fuzz.  Use rf_args_default() and then set fields.
+ * lcs_seq / indel / jaro / fuzz / osa / damerau_levenshtein.  Use rf_args_default() and then set fields.
  *   cutoff_usize : RF_NO_CUTOFF = NoScoreCutoff, else WithScoreCutoff(v) for the usize-valued ops
  *   cutoff_f64   : NaN = NoScoreCutoff, else WithScoreCutoff(v) for the f64-valued ops
  *   score_hint_* : results never depend on a hint (levenshtein.rs:2153-2160); in the reference it steers the CPU band search
@@ -161,7 +163,7 @@ typedef enum rf_mem { RF_MEM_HOST = 0, RF_MEM_DEVICE = 1 } rf_mem;
  *                  rf_topk_u32 with RF_OP_DISTANCE and no cutoff: the scan first runs under the
  *                  cutoff `hint` (a cutoff scan costs a fraction of a full one) and the k best are final if k candidates pass,
  *                  otherwise the hint doubles (past a quarter of the longest possible distance the plain scan runs).
- *                  Every other call ignores it.
+ *                  Every other call ignores it (damerau_levenshtein: so does the reference, damerau_levenshtein.rs:205).
  *
  * Three places where the device deliberately does NOT reproduce what release-mode rapidfuzz 0.5.0 returns (all tested,
  * tests/test_gpu_parity.py, all also in DESIGN.md section 3):
@@ -170,7 +172,9 @@ typedef enum rf_mem { RF_MEM_HOST = 0, RF_MEM_DEVICE = 1 } rf_mem;
  *       its result then DEPENDS on the hint (an upstream defect, reproduced by the oracle).  The device's hinted passes are exact and it
  *       returns the exact distance -- what the reference returns for every other hint.
  *   Q2  levenshtein similarity_with_args above its cutoff evaluates `maximum - usize::MAX` (details/distance.rs:209-210:
- *       a panic in debug builds, a wrapped value in release builds).  The device returns None.
+ *       a panic in debug builds, a wrapped value in release builds).  The device returns None.  The same for damerau_levenshtein,
+ *       whose _distance answers usize::MAX when the cutoff it is handed, maximum - score_cutoff, is below |len1 - len2|
+ *       (damerau_levenshtein.rs:183-185): None on the device.
  *   Q8  lcs_seq / indel / fuzz::ratio with a query of more than 64 symbols under a cutoff: the reference's banded multi-word LCS
  *       (lcs_seq.rs:297-331) moves the band's last block with ceil_div(row + 1 + band_width_left, 64) and so leaves out, for one
  *       row, the block that starts at bit row + 1 + band_width_left when that index is a multiple of 64.  A pair aligned along the
@@ -323,7 +327,7 @@ rf_status rf_release_caches(void);
 /* ---- one-vs-many ------------------------------------------------------------------------------
  * out[i] = scorer.<op>_with_args(candidate_i, &args) for every candidate, original order.
  *
- * rf_many_u32: the usize-valued methods of levenshtein / indel / lcs_seq / osa
+ * rf_many_u32: the usize-valued methods of levenshtein / indel / lcs_seq / osa / damerau_levenshtein
  *   (distance_with_args levenshtein.rs:1750-1777, similarity_with_args :1790-1817; indel.rs:464-521;
  *    lcs_seq.rs:893-949).  RF_NONE_U32 = None.
  * rf_many_f64: normalized_* of those metrics (levenshtein.rs:1670-1737 ...), all four methods of

@@ -66,7 +66,7 @@ void rf_args_default(rf_args* a)
 // ---------------------------------------------------------------------------------------------------
 rf_status rf_comparator_new(rf_metric metric, const uint8_t* s1, size_t len1, rf_comparator** out)
 try {
-    if (!out || (len1 && !s1) || (int)metric < 0 || (int)metric > (int)RF_OSA) {
+    if (!out || (len1 && !s1) || (int)metric < 0 || (int)metric > (int)RF_DAMERAU_LEVENSHTEIN) {
         set_error("rf_comparator_new: invalid argument");
         return RF_ERR_INVALID_ARG;
     }
@@ -94,7 +94,7 @@ RF_ABI_CATCH
 // corpus' symbol ids, the first time the comparator meets it (resolve()).
 rf_status rf_comparator_new_u32(rf_metric metric, const uint32_t* s1, size_t len1, rf_comparator** out)
 try {
-    if (!out || (len1 && !s1) || (int)metric < 0 || (int)metric > (int)RF_OSA) {
+    if (!out || (len1 && !s1) || (int)metric < 0 || (int)metric > (int)RF_DAMERAU_LEVENSHTEIN) {
         set_error("rf_comparator_new_u32: invalid argument");
         return RF_ERR_INVALID_ARG;
     }

@@ -1,6 +1,7 @@
 // rf_api_scan.hip -- plan(): Args x metric x op -> kernel parameters, and the rf_many_* / rf_one_* / rf_many_multi_* entry points (split out of rf_api.hip in round 4; rf_host.hpp has the shared declarations).
 // Product code: never includes or links anything from oracle/.
 #include "rf_host.hpp"
+#include "rf_dl_cell.hpp"
 
 extern "C" {
 
@@ -51,14 +52,14 @@ rf_status plan(const rf_comparator* c, const rf_corpus* corpus, rf_op op, const 
             }
     }
 
-    const bool usize_metric = c->metric == RF_LEVENSHTEIN || c->metric == RF_INDEL || c->metric == RF_LCS_SEQ || c->metric == RF_OSA;
+    const bool usize_metric = c->metric == RF_LEVENSHTEIN || c->metric == RF_INDEL || c->metric == RF_LCS_SEQ || c->metric == RF_OSA || c->metric == RF_DAMERAU_LEVENSHTEIN;
     const bool norm_op = op == RF_OP_NORMALIZED_DISTANCE || op == RF_OP_NORMALIZED_SIMILARITY;
     if ((int)op < 0 || (int)op > (int)RF_OP_NORMALIZED_SIMILARITY) {
         set_error("unknown rf_op");
         return RF_ERR_INVALID_ARG;
     }
     if (usize_metric && (norm_op != f64_out)) {
-        set_error("levenshtein/indel/lcs_seq: distance and similarity are u32-valued (rf_many_u32), normalized_* are "
+        set_error("levenshtein/indel/lcs_seq/osa/damerau_levenshtein: distance and similarity are u32-valued (rf_many_u32), normalized_* are "
                   "f64-valued (rf_many_f64)");
         return RF_ERR_INVALID_ARG;
     }
@@ -123,6 +124,35 @@ rf_status plan(const rf_comparator* c, const rf_corpus* corpus, rf_op op, const 
         *raw = RAW_OSA;
         p->finish = FIN_LEV;  // (beyond 512 symbols: long_kernel, with the transposition bit carried between word groups)
         break;
+    case RF_DAMERAU_LEVENSHTEIN: {  // damerau_levenshtein.rs:191-215; maximum = max(len1, len2), every op the MetricUsize default: FIN_LEV at factor 1
+        *raw = RAW_DL;
+        p->finish = FIN_LEV;
+        p->factor = 1;
+        // where the packed cells of rf_damerau.hip live, and how wide their four fields are
+        const uint64_t longest = std::max<uint64_t>(p->len1, corpus->max_len);
+        if (longest > DlCell16::kMaxLen) {
+            set_error("damerau_levenshtein: a query or candidate of 65535 symbols or more is beyond the 16-bit fields of the device's cells");
+            return RF_ERR_UNSUPPORTED;
+        }
+        p->dl_wide = longest > DlCell8::kMaxLen;
+        p->dl_reg = !p->dl_wide && p->len1 <= 64;
+        if (p->dl_reg) {
+            for (size_t i = 0; i < c->s1.size(); ++i) p->wf_query[i / 4] |= (uint32_t)corpus->sigma[c->s1[i]] << (8 * (i % 4));
+        } else {
+            const uint64_t row_bytes = std::max<uint64_t>(p->len1, 1) * kWave * (p->dl_wide ? sizeof(DlCell16::word) : sizeof(DlCell8::word));
+            const uint64_t lds_budget = 150u << 10;  // of the 160 KiB a gfx950 workgroup may hold
+            if (row_bytes + p->len1 + 16 > lds_budget) {
+                // one row of cells does not fit LDS (queries beyond ~300 symbols, which have the wide cells): one global scratch strip per wavefront instead
+                p->wf_global = 1;
+                p->wf_waves = kWavesPerBlock;
+                const uint64_t per_block = row_bytes * kWavesPerBlock, budget = 1ull << 30;
+                p->long_grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(budget / per_block, (uint64_t)scan_grid(corpus->n_tiles)));
+            } else {
+                p->wf_waves = (uint32_t)std::min<uint64_t>(kWavesPerBlock, (lds_budget - p->len1 - 16) / row_bytes);
+            }
+        }
+        break;
+    }
     case RF_INDEL:
         *raw = RAW_LCS;
         p->finish = FIN_INDEL;
@@ -246,7 +276,7 @@ rf_status plan(const rf_comparator* c, const rf_corpus* corpus, rf_op op, const 
         }
     }
 
-    if (*raw == RAW_WF) return RF_OK;
+    if (*raw == RAW_WF || *raw == RAW_DL) return RF_OK;  // the row-DP kernels: every tile, every column; the cutoff is emit_fin's compare
     // Long query + small distance cutoff (the reference's hyrroe2003_small_band_with_pm, levenshtein.rs:509-617, taken when
     // len1 > 64 and 2k + 1 <= 64, :1059-1062): one 64-bit word sliding down the diagonal instead of ceil(len1 / 64) words
     // per column.  k is the cutoff on the RAW distance (the common weight factor divided out).
@@ -364,6 +394,7 @@ static size_t launch_scratch_bytes(const ScanParams& p, RawKind raw)
 {
     const size_t waves = (size_t)p.long_grid * kWavesPerBlock;
     if (p.jaro_long) return waves * (((size_t)p.len1 + 63) / 64 + 1 + p.long_chunks_max) * kWave * sizeof(uint64_t);
+    if (p.wf_global && raw == RAW_DL) return waves * std::max<size_t>(p.len1, 1) * kWave * (p.dl_wide ? sizeof(DlCell16::word) : sizeof(DlCell8::word));  // dl_kernel's rows: one cell per query position
     if (p.wf_global) return waves * ((size_t)p.len1 + 1) * kWave * sizeof(uint32_t);
     if (p.long_words_pad) return waves * std::max<uint32_t>(1, p.long_chunks_max) * kWave * sizeof(uint32_t) * (raw == RAW_OSA ? 2 : 1);
     return 0;

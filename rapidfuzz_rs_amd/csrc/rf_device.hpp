@@ -1078,6 +1078,26 @@ __device__ __forceinline__ TileView load_tile(const ScanParams& p, uint32_t t)
 }
 
 
+// The row-DP kernels (rf_long.hip wf_kernel, rf_damerau.hip dl_kernel) compare symbols, not table rows: the query, renamed like the
+// corpus, rebuilt from the PM table into `qwords` words of LDS, 4 symbols per word (whole workgroup; synchronizes).
+__device__ __forceinline__ void stage_query_bytes(const ScanParams& p, uint32_t* lds_q, uint32_t qwords)
+{
+    uint8_t* q = reinterpret_cast<uint8_t*>(lds_q);
+    for (uint32_t i = threadIdx.x; i < qwords; i += blockDim.x) lds_q[i] = 0;
+    __syncthreads();
+    for (uint32_t c = threadIdx.x; c < 256; c += blockDim.x) {  // PM row c, bit i  <=>  s1[i] == c
+        const uint8_t stored = p.sigma[c];
+        for (uint32_t w = 0; w * 64 < p.len1; ++w) {
+            uint64_t bits = p.pm[(size_t)c * p.words + w];
+            while (bits) {
+                q[64 * w + (__ffsll((unsigned long long)bits) - 1)] = stored;
+                bits &= bits - 1;
+            }
+        }
+    }
+    __syncthreads();
+}
+
 // ScanParams::xcd_deal: the workgroup's place in the deal of tiles.  Workgroups go to the 8 XCDs round-robin, so workgroup w
 // takes the place (w % 8) * (grid / 8) + w / 8 and consecutive tiles are walked by workgroups of one XCD, at about the same time:
 // with the tiles ordered by origin (rf_api.hip tiles_by_origin) their result stores meet in that XCD's L2.

@@ -43,7 +43,8 @@ enum RawKind : uint32_t {
     RAW_LCS = 1,   // LCS length (Hyyro)
     RAW_JARO = 2,  // Jaro flags + transpositions
     RAW_WF = 4,    // generalized-weights Levenshtein, Wagner-Fischer rows in LDS
-    RAW_OSA = 3    // optimal string alignment distance (Hyyro + transposition term)
+    RAW_OSA = 3,   // optimal string alignment distance (Hyyro + transposition term)
+    RAW_DL = 5     // unrestricted Damerau-Levenshtein distance, row DP over packed cells (rf_damerau.hip)
 };
 
 // how the raw per-candidate primitive becomes the reference's return value
@@ -104,6 +105,8 @@ struct ScanParams {
     uint32_t wf_query[16];          // wf_reg_kernel: the (renamed) query bytes, 4 per word, for queries of <= 64 symbols
     uint32_t wf_global;             // wf_kernel: the DP row lives in long_scratch (global) instead of LDS: queries beyond ~590 symbols
     uint32_t wf_waves;              // wavefronts per workgroup of wf_kernel (LDS rows per wavefront: (len1 + 1) * 256 B)
+    uint32_t dl_reg;                // rf_damerau.hip: 1 = dl_reg_kernel (query <= 64 and max(len1, longest candidate) <= 254: wf_query holds the query), 0 = dl_kernel,
+    uint32_t dl_wide;               // whose cells have 8-bit fields (0: nothing beyond 254 symbols) or 16-bit fields (1); rows in LDS or global by wf_waves / wf_global
     uint32_t tile_step;             // >= 1: visit every tile_step-th tile of the range (the top-k bound sample)
     uint32_t head_need, head_k;     // head-plane cutoff scans: >= head_need of the first 8 symbols must have a partner within head_k positions (0 = filter off)
     // head_filter_kernel's product: the tiles a cutoff scan still has to walk ([0] = their number, then the tiles); tile_list_buf is
@@ -176,7 +179,7 @@ struct ScanParams {
     uint32_t topk_bound_from_result;  // sample pass: leave (k-th best key + 1) in *topk_bound for the main scan
 };
 
-// kernel launchers (rf_scan.hip, rf_long.hip, rf_jaro.hip, rf_pack.hip)
+// kernel launchers (rf_scan.hip, rf_long.hip, rf_damerau.hip, rf_jaro.hip, rf_pack.hip)
 hipError_t launch_scan(RawKind raw, const ScanParams& p, hipStream_t stream, int* grid_used);
 hipError_t launch_osa1_asm(const ScanParams& p, hipStream_t stream, int grid);   // the same around the OSA column (OsaState<1>)
 hipError_t launch_lev32_asm(const ScanParams& p, hipStream_t stream, int grid);  // the same for queries of <= 32 symbols (Lev32State)
@@ -213,6 +216,7 @@ hipError_t launch_lane_list_pack(uint32_t* buf, uint32_t G, uint32_t cap, uint32
 hipError_t launch_scan_mixed(RawKind raw, const ScanParams& p, hipStream_t stream);  // p.mixed / tile_begin / tile_end: the mixed section
 hipError_t launch_long(RawKind raw, const ScanParams& p, hipStream_t stream, int grid);
 hipError_t launch_wf(const ScanParams& p, hipStream_t stream);
+hipError_t launch_dl(const ScanParams& p, hipStream_t stream);  // rf_damerau.hip
 hipError_t launch_jaro(const ScanParams& p, hipStream_t stream);
 hipError_t launch_scan_multi(RawKind raw, bool narrow, const ScanParams& p, hipStream_t stream);
 hipError_t launch_topk_final(const uint64_t* keys, uint32_t count, uint32_t k, uint64_t* out, hipStream_t stream);

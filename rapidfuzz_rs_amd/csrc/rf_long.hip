@@ -22,20 +22,7 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void wf_kernel(const ScanPar
     extern __shared__ uint32_t lds_wf[];
     const uint32_t len1 = p.len1;
     const uint32_t qwords = (len1 + 3) / 4 + 1;  // query bytes, 4 per word, one word of slack
-    uint8_t* lds_q = reinterpret_cast<uint8_t*>(lds_wf);
-    for (uint32_t i = threadIdx.x; i < qwords; i += blockDim.x) lds_wf[i] = 0;
-    __syncthreads();
-    for (uint32_t c = threadIdx.x; c < 256; c += blockDim.x) {  // PM row c, bit i  <=>  s1[i] == c
-        const uint8_t stored = p.sigma[c];
-        for (uint32_t w = 0; w * 64 < len1; ++w) {
-            uint64_t bits = p.pm[(size_t)c * p.words + w];
-            while (bits) {
-                lds_q[64 * w + (__ffsll((unsigned long long)bits) - 1)] = stored;
-                bits &= bits - 1;
-            }
-        }
-    }
-    __syncthreads();
+    stage_query_bytes(p, lds_wf, qwords);
 
     const uint32_t lane = threadIdx.x & (kWave - 1);
     const uint32_t wave = uniform(threadIdx.x / kWave);

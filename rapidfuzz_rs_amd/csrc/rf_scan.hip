@@ -1292,6 +1292,7 @@ hipError_t launch_scan(RawKind raw, const ScanParams& p_in, hipStream_t stream, 
     case RAW_LCS: return p.len1 <= 32 ? launch_state<Lcs32State>(raw, p, stream, grid) : launch_words<LcsState>(raw, p, stream, grid);
     case RAW_OSA: return launch_words<OsaState>(raw, p, stream, grid);
     case RAW_WF: return launch_wf(p, stream);
+    case RAW_DL: return launch_dl(p, stream);
     case RAW_JARO: return launch_jaro(p, stream);
     default: return hipErrorInvalidValue;
     }

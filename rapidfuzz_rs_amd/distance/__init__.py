@@ -6,7 +6,8 @@ levenshtein = _M("levenshtein", _N.LEVENSHTEIN, False)    # src/distance/levensh
 indel = _M("indel", _N.INDEL, False)                      # src/distance/indel.rs
 lcs_seq = _M("lcs_seq", _N.LCS_SEQ, False)                # src/distance/lcs_seq.rs
 osa = _M("osa", _N.OSA, False)                            # src/distance/osa.rs
+damerau_levenshtein = _M("damerau_levenshtein", _N.DAMERAU_LEVENSHTEIN, False)  # src/distance/damerau_levenshtein.rs
 jaro = _M("jaro", _N.JARO, True)                          # src/distance/jaro.rs
 jaro_winkler = _M("jaro_winkler", _N.JARO_WINKLER, True)  # src/distance/jaro_winkler.rs
 
-__all__ = ["levenshtein", "indel", "lcs_seq", "osa", "jaro", "jaro_winkler"]
+__all__ = ["levenshtein", "indel", "lcs_seq", "osa", "damerau_levenshtein", "jaro", "jaro_winkler"]
