@@ -1,6 +1,7 @@
 """damerau_levenshtein::BatchComparator on the device (rf_damerau.hip), bit-exact against tests/dl_reference.py: the reference's known answers,
 parity over corpus shapes x query lengths x ops x cutoffs (the register kernels, the LDS rows with 8- and 16-bit fields, the global rows), every
 result road, two pack-time layouts through child processes, and a randomized differential test.
+Here every wavefront walks ONE tile; several tiles per wavefront of each of these kernels: tests/multitile_rowdp_check.py, mode "damerau" (started by tests/test_gpu_parity.py).
 
 The inputs are chosen so that a kernel computing a NEIGHBOURING metric fails: near-duplicates are planted by "swap two adjacent symbols and insert
 a random symbol between them" (four times, clipped to 64) -- one transposition-with-insertion costs 2 here and 3 in OSA -- and the tests assert from the

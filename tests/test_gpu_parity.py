@@ -2449,6 +2449,38 @@ def test_asm_kernels_many_tiles_per_wavefront(mode):
     assert "FAILURES 0" in r.stdout
 
 
+# mode -> (argv[1] of tests/multitile_rowdp_check.py, extra environment, timeout in seconds: about three times the seconds measured on an MI355X
+# (tests/multitile_rowdp_check.py MEASURED_SECONDS), and at least 60: the child imports torch and loads the library on a shared machine)
+ROWDP_MODES = {
+    "damerau": ("damerau", {}, 60),
+    "weights": ("weights", {}, 100),
+    "weights-lds": ("weights", {"RF_WF_REG": "0"}, 60),
+    "long": ("long", {}, 60),
+    "mixed": ("mixed", {}, 60),
+    "cutoff": ("cutoff", {}, 60),
+}
+
+
+@pytest.mark.parametrize("mode", list(ROWDP_MODES))
+def test_scan_grid_kernels_many_tiles_per_wavefront(mode):
+    """RF_SCAN_BLOCKS_PER_CU_FULL (the test above) shrinks scan_grid_full() only.  Everything launched on scan_grid() -- dl_reg_kernel / dl_kernel, wf_reg_kernel /
+    wf_kernel, long_kernel, jaro_long_kernel, scan_kernel_mixed, the cutoff early-out scans, the band kernels -- owns a second tile per wavefront only beyond CUs x 32 x 4 tiles at the
+    default of 32 workgroups per CU.  tests/multitile_rowdp_check.py runs in a subprocess with RF_SCAN_BLOCKS_PER_CU=1 (the knob is read once, before the first
+    launch) over corpora sized from the CU count so that every wavefront of the launch under test walks >= 4 tiles (tests/test_scan_grid.py holds the arithmetic),
+    every value against tests/dl_reference.py / the oracle.  One child per mode, started once."""
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    arg, extra, limit = ROWDP_MODES[mode]
+    env = dict(os.environ, RF_SCAN_BLOCKS_PER_CU="1", **extra)
+    r = subprocess.run([sys.executable, os.path.join(root, "tests", "multitile_rowdp_check.py"), arg], capture_output=True, text=True, cwd=root, env=env, timeout=limit)
+    assert r.returncode == 0, (r.stdout[-4000:], r.stderr[-2000:])
+    assert "FAILURES 0" in r.stdout
+    lines = [ln for ln in r.stdout.splitlines() if "tiles/wavefront>=" in ln]
+    assert lines and all(ln.endswith(" ok") and int(ln.split("tiles/wavefront>=")[1].split()[0]) >= 4 for ln in lines), r.stdout[-4000:]
+
+
 @pytest.mark.parametrize("mode", ["rows", "ragged", "ragged-gather-all", "ragged-storage-order", "ragged-by-origin-all", "ragged-by-origin-no-deal", "ragged-default-grid"])
 def test_multiword_levenshtein_band_trimming(mode):
     """the multi-word Levenshtein scans skip the words outside the Ukkonen band of each 16-column chunk
