@@ -25,7 +25,7 @@
  * There is no variable that changes a result: the measurement switches that do (RF_EXP_NOHBM, RF_EXP_TILE_BYTES) are compiled only into
  * -DRF_EXPERIMENTS builds (tools/build_stream_variant.sh), never into librfgpu.so (tests/test_abi.py checks the binary).
  *   name                          default   meaning
- *   RF_SCAN_BLOCKS_PER_CU         32        workgroups per CU of short-running launches (cutoff scans, band kernel, long queries)
+ *   RF_SCAN_BLOCKS_PER_CU         32        workgroups per CU of short-running launches (cutoff scans, band kernel, long queries); caps the grids of the list-walking launches too
  *   RF_SCAN_BLOCKS_PER_CU_FULL    256       most workgroups per CU of full (no-cutoff) scans
  *   RF_SCAN_TILES_PER_WAVE        5         tiles per wavefront the grid of a full scan aims at (below the cap above; at least 32 workgroups per CU)
  *   RF_STREAM                     1         0: scan_body instead of the streaming loop of the compiled scans

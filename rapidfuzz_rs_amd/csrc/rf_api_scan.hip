@@ -972,6 +972,8 @@ static rf_status run_many_hinted(const rf_comparator* c_in, const rf_corpus* cor
             if (report && report[10] != 0) {  // the last such call on this stream: did its first pass leave more than 30 % of the corpus?
                 const uint64_t left = report[8], of = report[9];
                 report[10] = 0;
+                const bool trace_report = sw_trace_plan();
+                if (trace_report) std::fprintf(stderr, "[rf plan] hint report: the last list scan on this stream walked %llu survivors of %llu candidates\n", (unsigned long long)left, (unsigned long long)of);
                 if (left * 10 > of * 3) {
                     corpus->hint_trust.store(0, std::memory_order_relaxed);
                     go = false;
@@ -1285,6 +1287,9 @@ rf_status run_many(const rf_comparator* c_in, const rf_corpus* corpus_in, rf_op 
             static const bool adapt = env_on("RF_BAND_DEFER_ADAPT");
             volatile uint32_t* report = tl->report();
             p.band_report = const_cast<uint32_t*>(report);
+            const bool trace_report = sw_trace_plan();
+            if (trace_report && report && report[3] != 0)
+                std::fprintf(stderr, "[rf plan] band report: the last hand-over launch on this stream listed %u entries, %u survivors of %u tiles, band_k=%u\n", report[0], report[1], report[2], report[7]);
             if (adapt && report) {
                 bool pays = false;
                 if (report[3] != 0) {

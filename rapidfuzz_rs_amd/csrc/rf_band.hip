@@ -246,9 +246,9 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void band_sparse_kernel(cons
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         if (p.band_defer_seen) *p.band_defer_seen = 0;  // (the first pass' count of hand-over candidates: zero again for this stream's next launch)
         if (p.band_report) {  // what the first pass listed, for the host's choice of the next launch's form (rf_api_scan.hip run_many; read there without waiting)
-            const uint32_t words[7] = {entries, total, p.tile_end - p.tile_begin, 1u, p.band_defer_at, p.band_defer_max, p.uniform_len};
+            const uint32_t words[8] = {entries, total, p.tile_end - p.tile_begin, 1u, p.band_defer_at, p.band_defer_max, p.uniform_len, p.band_k};
 #pragma unroll
-            for (int i = 0; i < 7; ++i) __hip_atomic_store(p.band_report + i, words[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            for (int i = 0; i < 8; ++i) __hip_atomic_store(p.band_report + i, words[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
     if (blockIdx.x * kWavesPerBlock >= n_dense) return;  // (the survivors' number is only known here)

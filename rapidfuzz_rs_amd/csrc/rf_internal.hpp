@@ -161,7 +161,7 @@ struct ScanParams {
     uint32_t band_asm;              // 1: full eight-column diagonal runs as one asm block (rf_band_asm.inc; set by the launcher)
     uint32_t band_defer_at, band_defer_max, band_defer_after;  // != 0 (set by the launcher): a tile with <= band_defer_max lanes within break_score at column band_defer_at is listed for band_sparse_kernel, once the launch has seen band_defer_after of them
     uint32_t* band_defer_seen;      // that count (the list buffer's trailer, ListLayout::trailer_at(); band_sparse_kernel zeroes it again)
-    uint32_t* band_report;          // pinned host words (or nullptr): band_sparse_kernel leaves [0] tiles listed, [1] lanes listed, [2] tiles of the launch, [3] 1, [4] band_defer_at, [5] band_defer_max, [6] the launch's candidate length; [8..10]: sparse_words_kernel's (lanes listed, candidates, 1)
+    uint32_t* band_report;          // pinned host words (or nullptr): band_sparse_kernel leaves [0] tiles listed, [1] lanes listed, [2] tiles of the launch, [3] 1, [4] band_defer_at, [5] band_defer_max, [6] the launch's candidate length, [7] its band_k; [8..10]: sparse_words_kernel's (lanes listed, candidates, 1)
     uint32_t band_list;             // 1 (score_hint, first pass): the band launch lists every tile that holds lanes it answered None, with their mask (tile_list_buf), for launch_sparse_words
     // the multi-word asm scans (rf_stream_asm.hip, tools/gen_stream_asm.py BlockKind): raw distances above trim_k1 - 1 need not be exact (they must come out above
     // it), which narrows the Ukkonen band the kernels trim their word-columns to; 0 = no bound beyond max(len1, len2)
@@ -240,6 +240,7 @@ hipError_t launch_ragged_scatter_mixed(const uint8_t* bytes, uint64_t first, con
                                        const uint32_t* pool_len, const uint32_t* pool_spos, const uint32_t* pool_vslot0, const uint8_t* sigma, uint8_t* packed, uint32_t* orig,
                                        uint32_t* mixed_orig, hipStream_t st);
 int scan_max_grid();
+int list_max_grid(int per_cu);  // CUs x min(per_cu, RF_SCAN_BLOCKS_PER_CU): the grids of the launches that walk survivor lists
 // results of a ragged corpus in original order without scattered stores (rf_pack.hip): slot -> slot / candidate -> slot maps, and the gather
 hipError_t launch_slot_maps(const uint32_t* orig, uint32_t n_slots, uint32_t* slot_of, uint32_t* ident, hipStream_t stream);
 hipError_t launch_head8_plane(const uint8_t* data, uint32_t n_tiles, uint32_t tile_bytes, uint8_t* heads, hipStream_t stream);  // rf_pack.hip: the candidates' first 8 symbols

@@ -5,6 +5,7 @@
 //   topk_final_kernel             selection of the k best candidate keys
 // Device helpers live in rf_device.hpp; the long-pattern, generalized-weights and Jaro kernels in rf_long.hip / rf_jaro.hip.
 #include <atomic>
+#include <cstdio>
 #include <type_traits>
 
 #include "rf_device.hpp"
@@ -973,11 +974,19 @@ static int device_cus()
     return n;
 }
 static int positive_or(long long v, int dflt) { return v > 0 ? (int)v : dflt; }  // (RF_SCAN_*: <= 0 means the default)
-int scan_max_grid()
+static int scan_blocks_per_cu()
 {
     static const int per_cu = positive_or(env_int("RF_SCAN_BLOCKS_PER_CU", 0), 32);
+    return per_cu;
+}
+int scan_max_grid()
+{
+    const int per_cu = scan_blocks_per_cu();
     return device_cus() * per_cu;
 }
+// The launches that walk a LIST of survivors (rf_sparse.hip, the head plane's two passes) size their grids by factors of their own, all <= 32 per CU: the knob caps
+// them too, so that RF_SCAN_BLOCKS_PER_CU=1 gives their wavefronts several units each (tests/multitile_lists_check.py); unset, every such grid is what its factor says.
+int list_max_grid(int per_cu) { return device_cus() * std::min(per_cu, scan_blocks_per_cu()); }
 int scan_max_grid_full()
 {
     static const int per_cu = positive_or(env_int("RF_SCAN_BLOCKS_PER_CU_FULL", 0), 256);
@@ -997,7 +1006,7 @@ static bool sw_lane_compact() { static const bool v = env_on("RF_LANE_COMPACT");
 static ListLayout head_list_layout(const ScanParams& p, ListLayout::Kind kind)
 {
     const uint32_t pairs = (p.tile_end - p.tile_begin + 1) / 2;
-    const uint32_t fgrid = std::min<uint32_t>((pairs + kWavesPerBlock - 1) / kWavesPerBlock, std::min<uint32_t>((uint32_t)device_cus() * 16u, 4096u));
+    const uint32_t fgrid = std::min<uint32_t>((pairs + kWavesPerBlock - 1) / kWavesPerBlock, std::min<uint32_t>((uint32_t)list_max_grid(16), 4096u));
     return ListLayout::head(kind, pairs, fgrid * kWavesPerBlock);
 }
 
@@ -1020,6 +1029,16 @@ EarlyRoad early_road(RawKind raw, const ScanParams& p)
     const bool lanes = p.lane_list && sw_lane_compact();
     if (!head_list_layout(p, lanes ? ListLayout::kLanes : ListLayout::kTiles).fits(p.tile_list_words)) return EarlyRoad::Head8;
     return lanes ? EarlyRoad::TwoPassLanes : EarlyRoad::TwoPassTiles;
+}
+
+// RF_TRACE_PLAN: which of the two-pass roads a cutoff launch takes, and the shape of its listing pass (what a test of several units per wavefront holds its sizes to)
+static void trace_two_pass_road(EarlyRoad road, const ScanParams& p)
+{
+    if (road != EarlyRoad::TwoPassLanes && road != EarlyRoad::TwoPassTiles) return;
+    const bool lanes = road == EarlyRoad::TwoPassLanes;
+    const ListLayout L = head_list_layout(p, lanes ? ListLayout::kLanes : ListLayout::kTiles);
+    std::fprintf(stderr, "[rf road] two-pass: %s list, %u tiles, %u listing wavefronts, %u entries per segment, run=%d topk=%u\n", lanes ? "lane" : "tile", p.tile_end - p.tile_begin, L.G,
+                 L.cap, p.run_orig != nullptr, p.topk_k);
 }
 
 // pn: p with the launcher's own switches (narrow_look, exp_flags) filled in
@@ -1065,7 +1084,7 @@ static hipError_t launch_early(EarlyRoad road, const ScanParams& p, const ScanPa
         else
             hipLaunchKernelGGL((head_filter_kernel<State, J, false>), fg, b, 0, stream, pn, buf, L.cap);
         hipLaunchKernelGGL(tile_list_pack_kernel, pg, dim3(256), 0, stream, buf, L.G, L.cap);
-        hipLaunchKernelGGL((early_lean_kernel<State, J>), dim3((uint32_t)device_cus() * 8u), b, 0, stream, p2);
+        hipLaunchKernelGGL((early_lean_kernel<State, J>), dim3((uint32_t)list_max_grid(8)), b, 0, stream, p2);
     } else {
         return hipErrorInvalidValue;  // (early_road() sends no other state down the head-plane roads)
     }
@@ -1151,6 +1170,8 @@ static hipError_t launch_state(RawKind raw, const ScanParams& p, hipStream_t str
             pn.exp_flags = 0u;
 #endif
             const EarlyRoad road = early_road(raw, p);
+            const bool trace_road = sw_trace_plan();
+            if (trace_road) trace_two_pass_road(road, p);
             if (road != EarlyRoad::RunTime) {
                 switch (p.first_check) {
                 case 4: return launch_early<State, 4>(road, p, pn, stream, g);

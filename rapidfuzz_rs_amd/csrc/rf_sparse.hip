@@ -225,13 +225,12 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void sparse_words_kernel(con
 
 hipError_t launch_sparse_lean(int state_kind, const ScanParams& p, hipStream_t stream)
 {
-    // (the survivors' number is only known on the device: a fixed grid of 8 workgroups per CU, like early_lean_kernel over its list)
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+    // (the survivors' number is only known on the device: a grid sized by the tiles of the launch, at most list_max_grid() of 32 workgroups per CU -- 8 with top-k
+    // lists or over a length run, like early_lean_kernel over its list -- which RF_SCAN_BLOCKS_PER_CU caps)
     const uint32_t tiles = p.tile_end > p.tile_begin ? p.tile_end - p.tile_begin : 1u;
     // (a wavefront per dense tile while they are few: a tile is a chain of dependent loads -- list entry, chunk rows -- and the workgroups beyond the survivors leave at once)
     // (a length run of a bucketed corpus is one of several launches of its call and a fraction of the corpus: the smaller grid, or the empty workgroups of eight runs add up)
-    const uint32_t want = (uint32_t)cus * ((p.topk_k || p.run_orig) ? 8u : 32u), most = (tiles + kWavesPerBlock - 1) / kWavesPerBlock;
+    const uint32_t want = (uint32_t)list_max_grid((p.topk_k || p.run_orig) ? 8 : 32), most = (tiles + kWavesPerBlock - 1) / kWavesPerBlock;
     const dim3 g(std::max(1u, std::min(want, most))), b(kWave * kWavesPerBlock);
     switch (state_kind) {
     case 0: hipLaunchKernelGGL((sparse_lean_kernel<LevState<1>>), g, b, 0, stream, p); break;
@@ -244,10 +243,8 @@ hipError_t launch_sparse_lean(int state_kind, const ScanParams& p, hipStream_t s
 
 hipError_t launch_sparse_words(const ScanParams& p, hipStream_t stream)
 {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
     const uint32_t tiles = p.tile_end > p.tile_begin ? p.tile_end - p.tile_begin : 1u;
-    const dim3 g(std::max(1u, std::min((uint32_t)cus * 16u, (tiles + kWavesPerBlock - 1) / kWavesPerBlock))), b(kWave * kWavesPerBlock);
+    const dim3 g(std::max(1u, std::min((uint32_t)list_max_grid(16), (tiles + kWavesPerBlock - 1) / kWavesPerBlock))), b(kWave * kWavesPerBlock);
     switch (p.words) {
     case 2: hipLaunchKernelGGL((sparse_words_kernel<LevState<2>>), g, b, 0, stream, p); break;
     case 3: hipLaunchKernelGGL((sparse_words_kernel<LevState<3>>), g, b, 0, stream, p); break;

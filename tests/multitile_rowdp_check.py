@@ -26,10 +26,10 @@ exit status 0 = all equal.  A mismatch is a value: the mode runs to its end.  A 
   cutoff   the default roads of the cutoff scans (early-out scans, the band kernels, the band pass of the hinted scan, filter_many, topk), oracle, with quirk
            Q8's excuse as test_gpu_parity._check_many has it.  The figure printed is that of the first pass, which runs on scan_grid() / band_grid_of().
 
-What RF_SCAN_BLOCKS_PER_CU does NOT reach, so that no figure is printed for it: the launches that walk a list of survivors.  sparse_lean_kernel and
-sparse_words_kernel run on CUs x 8 / 16 / 32 workgroups (rf_sparse.hip), the head plane's first pass on head_list_layout's min(ceil(pairs / 4), CUs x 16, 4096) and
-its second pass on CUs x 8 (rf_scan.hip); none reads the knob, and their lists are as long as the data makes them (about 1 % of the corpus here).  The hint kernels
-(rf_hint.hip) take scan_grid(units) with `units` survivors.  Several units per wavefront of those is a matter of survivor counts against THEIR grids, not of this file.
+The launches that walk a list of survivors are not this file's: sparse_lean_kernel and sparse_words_kernel (rf_sparse.hip), the head plane's listing pass and its
+second pass over a tile list (rf_scan.hip), band_sparse_kernel.  Since list_max_grid() (rf_scan.hip) the knob caps their grids as well -- the second passes of the
+cutoff mode here run on the capped grids too -- but several units per wavefront there is a matter of SURVIVOR counts, and tests/multitile_lists_check.py sizes
+corpora for that, one mode per launch.  The hint kernels (rf_hint.hip) take scan_grid(units) with `units` survivors.
 
 Seconds per mode, measured once on an MI355X (256 CUs: 262 117 candidates per corpus at 4 wavefronts per workgroup, 131 045 at 2, 65 509 at 1; the bucketed
 corpus of query 64 has 488 861, the ragged Jaro corpora 262 181): MEASURED_SECONDS below; the timeouts of the test are about three times these, and at least 60 s.

@@ -2467,7 +2467,8 @@ def test_scan_grid_kernels_many_tiles_per_wavefront(mode):
     wf_kernel, long_kernel, jaro_long_kernel, scan_kernel_mixed, the cutoff early-out scans, the band kernels -- owns a second tile per wavefront only beyond CUs x 32 x 4 tiles at the
     default of 32 workgroups per CU.  tests/multitile_rowdp_check.py runs in a subprocess with RF_SCAN_BLOCKS_PER_CU=1 (the knob is read once, before the first
     launch) over corpora sized from the CU count so that every wavefront of the launch under test walks >= 4 tiles (tests/test_scan_grid.py holds the arithmetic),
-    every value against tests/dl_reference.py / the oracle.  One child per mode, started once."""
+    every value against tests/dl_reference.py / the oracle.  One child per mode, started once.  (The knob caps the grids of the launches that walk survivor lists
+    too, list_max_grid(); giving THEIR wavefronts several units takes corpora sized by survivors: test_list_walking_kernels_many_units_per_wavefront below.)"""
     import subprocess
     import sys
 
@@ -2479,6 +2480,49 @@ def test_scan_grid_kernels_many_tiles_per_wavefront(mode):
     assert "FAILURES 0" in r.stdout
     lines = [ln for ln in r.stdout.splitlines() if "tiles/wavefront>=" in ln]
     assert lines and all(ln.endswith(" ok") and int(ln.split("tiles/wavefront>=")[1].split()[0]) >= 4 for ln in lines), r.stdout[-4000:]
+
+
+# mode -> (argv[1] of tests/multitile_lists_check.py, extra environment, timeout in seconds: about three times the seconds measured on an MI355X
+# (tests/multitile_lists_check.py MEASURED_SECONDS), and at least 60)
+LISTS_MODES = {
+    "lanes": ("lanes", {"RF_HEAD8_MIN": "1", "RF_BAND_FILTER": "1"}, 60),
+    "lanes-head8": ("lanes", {"RF_HEAD8_MIN": "1", "RF_BAND_FILTER": "1", "RF_HEAD6": "0"}, 60),
+    "tiles": ("tiles", {"RF_HEAD8_MIN": "1", "RF_BAND_FILTER": "1", "RF_LANE_COMPACT": "0"}, 60),
+    "runs": ("runs", {"RF_HEAD8_MIN": "1", "RF_BAND_FILTER": "1"}, 60),
+    "hint": ("hint", {"RF_HINT_SAMPLE_MIN_TILES": "1"}, 60),
+    "band": ("band", {"RF_BAND_DEFER_ADAPT": "0"}, 60),
+    "band-compiled": ("band", {"RF_BAND_DEFER_ADAPT": "0", "RF_ASM_BAND": "0"}, 60),
+}
+
+@pytest.mark.parametrize("mode", list(LISTS_MODES))
+def test_list_walking_kernels_many_units_per_wavefront(mode):
+    """The launches that walk a LIST of survivors -- head_filter_kernel (a wavefront per pair of tiles), lane_list_pack_kernel / tile_list_pack_kernel (a thread per
+    segment), sparse_lean_kernel, early_lean_kernel over a tile list, sparse_words_kernel, band_sparse_kernel -- run on CUs x 8 / 16 / 32 workgroups (half of band_grid_of()
+    for the last): a wavefront owns a second unit only when the survivors outnumber CUs x 32 x 4 x 64.  list_max_grid() (rf_scan.hip) caps those factors by
+    RF_SCAN_BLOCKS_PER_CU; tests/multitile_lists_check.py runs in a subprocess with the knob at 1 over corpora sized from the CU count so that every wavefront of the
+    launch under test owns >= 10 dense tiles and 5 pairs (lanes, shape A) or >= 4 units (everything else), asserts that from its inputs or from the RF_TRACE_PLAN
+    trace before it looks at a value, and compares every value with the oracle.  One child per mode, started once."""
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    arg, extra, limit = LISTS_MODES[mode]
+    env = dict(os.environ, RF_SCAN_BLOCKS_PER_CU="1", RF_TRACE_PLAN="1", **extra)
+    r = subprocess.run([sys.executable, os.path.join(root, "tests", "multitile_lists_check.py"), arg], capture_output=True, text=True, cwd=root, env=env, timeout=limit)
+    assert r.returncode == 0, (r.stdout[-4000:], r.stderr[-2000:])
+    assert "FAILURES 0" in r.stdout
+    lines = [ln for ln in r.stdout.splitlines() if "units/wavefront>=" in ln]
+    assert lines, r.stdout[-4000:]
+    import multitile_lists_check as LC  # (the floors are the checker's own table)
+
+    assert LC.FLOOR["lanes A"] == 10 and LC.FLOOR["lanes A pairs"] == 5 and all(LC.FLOOR[k] == 4 for k in ("lanes B", "tiles", "runs", "hint", "band"))
+    for ln in lines:
+        floor = next(v for k, v in LC.FLOOR.items() if ln.startswith(k))
+        assert ln.endswith(" ok") and int(ln.split("units/wavefront>=")[1].split()[0]) >= floor, ln
+        if ln.startswith("lanes A"):
+            assert int(ln.split("pairs/wavefront>=")[1].split()[0]) >= LC.FLOOR["lanes A pairs"], ln
+    if arg == "hint":
+        assert "[rf plan] hint lists:" in r.stderr
 
 
 @pytest.mark.parametrize("mode", ["rows", "ragged", "ragged-gather-all", "ragged-storage-order", "ragged-by-origin-all", "ragged-by-origin-no-deal", "ragged-default-grid"])
