@@ -187,6 +187,20 @@ public:
         return res;
     }
 
+    // ---- the k best candidates of every query, one call (rf_topk_multi_u32): res[j] = (index_base + index, score) pairs of scorers[j], best first -- ordered by
+    // (score ascending, index ascending), at most k of them.  Fusable queries share passes over the corpus; no [q][n] matrix is built.  usize metrics only.
+    static std::vector<std::vector<std::pair<uint64_t, size_t>>> distance_topk_multi(const std::vector<const BatchComparator*>& scorers, const Corpus& c, uint32_t k,
+                                                                                      const Args<usize_result>& a = {}, uint64_t index_base = 0)
+    {
+        return topk_multi(scorers, c, k, RF_OP_DISTANCE, a.to_c(), index_base);
+    }
+    /// the same by similarity: (score descending, index ascending)
+    static std::vector<std::vector<std::pair<uint64_t, size_t>>> similarity_topk_multi(const std::vector<const BatchComparator*>& scorers, const Corpus& c, uint32_t k,
+                                                                                        const Args<usize_result>& a = {}, uint64_t index_base = 0)
+    {
+        return topk_multi(scorers, c, k, RF_OP_SIMILARITY, a.to_c(), index_base);
+    }
+
     // ---- the reference's per-candidate methods (a one-candidate corpus through the same kernels)
     std::optional<usize_result> distance_with_args(std::string_view s2, const Args<usize_result>& a) const
     {
@@ -227,6 +241,22 @@ private:
             for (size_t i = 0; i < out.size(); ++i)
                 if (out[i] != RF_NONE_U32) res[i] = out[i];
         }
+        return res;
+    }
+    static std::vector<std::vector<std::pair<uint64_t, size_t>>> topk_multi(const std::vector<const BatchComparator*>& scorers, const Corpus& c, uint32_t k, rf_op op,
+                                                                            const rf_args& a, uint64_t index_base)
+    {
+        static_assert(!FloatMetric, "rf_topk_multi_u32 serves the usize-valued metrics");
+        std::vector<const rf_comparator*> hs;
+        for (const BatchComparator* s : scorers) hs.push_back(s->h_);
+        const size_t q = hs.size();
+        if (q == 0) return {};  // (an empty vector has no data(): the C ABI refuses a null list even of no queries)
+        std::vector<uint32_t> score(q * k), count(q);
+        std::vector<uint64_t> index(q * k);
+        check(rf_topk_multi_u32(hs.data(), (uint32_t)q, c.handle(), op, &a, k, index_base, score.data(), index.data(), count.data(), nullptr));
+        std::vector<std::vector<std::pair<uint64_t, size_t>>> res(q);
+        for (size_t j = 0; j < q; ++j)
+            for (uint32_t m = 0; m < count[j]; ++m) res[j].emplace_back(index[j * k + m], (size_t)score[j * k + m]);
         return res;
     }
     template <class T>

@@ -69,6 +69,7 @@
  *   RF_GATHER_SPAN / RF_GATHER_UNROLL   16384 / 8   window gather tuning
  *   RF_TOPK_VIA_SCORES            1         top-k (k <= 64) as scan + one pass over the scores: 0 never, 1 multi-word Levenshtein, 2 every shape with an asm scan
  *   RF_TOPK_SAMPLE                1024      tiles of the in-scan top-k's bound sample (0: no sample pass)
+ *   RF_TOPK_MULTI                 1         0: rf_topk_multi_u32 sends every query through rf_topk_u32 instead of fusing 4 (or 2) to a pass over the corpus
  *   RF_JARO_PRIV                  0         1: Jaro asm kernel gathers from a conflict-free copy of the pattern table (corpora of <= 64 symbols; measured: no gain)
  *   RF_WF_REG                     1         0: LDS rows instead of register rows for generalized weights, queries <= 64
  *   RF_TRANSLATE_DIRECT           1         0: staged translation of u32 overflow symbols
@@ -385,6 +386,25 @@ rf_status rf_many_multi_u32(const rf_comparator *const *cs, uint32_t q, const rf
                             const rf_args *args, uint32_t *out, rf_mem out_mem, void *stream);
 rf_status rf_many_multi_f64(const rf_comparator *const *cs, uint32_t q, const rf_corpus *corpus, rf_op op,
                             const rf_args *args, double *out, rf_mem out_mem, void *stream);
+
+/* ---- top-k for many queries x one corpus --------------------------------------------------------
+ * Row j is exactly what rf_topk_u32(cs[j], corpus, op, args, k, index_base, ...) returns (see "top-k" below: drop None, order by
+ * (score, index), keep the first k; the same tie rule, the same index_base, any k >= 1), with the same `args` for every query as in
+ * rf_many_multi_*.  op is RF_OP_DISTANCE or RF_OP_SIMILARITY.  Outputs are HOST arrays: out_score and out_index row-major [q][k],
+ * out_count[q]; only the first out_count[j] entries of row j are defined.
+ * Queries that rf_many_multi_* would fuse -- levenshtein (uniform or Indel-like weights) / indel / lcs_seq, <= 64 symbols, no tight
+ * cutoff, k <= 64 -- are evaluated 4 (or 2) at a time by ONE pass over the corpus that keeps a k-entry list per query inside the scan
+ * and returns q x k entries: no [q][n] matrix exists at any point.  Every other query (osa, damerau_levenshtein, general weight
+ * tables, longer queries, a tight cutoff, a u32 query with overflow-class symbols, the odd one left over, every query when k > 64)
+ * goes through rf_topk_u32 itself, one call per query.  RF_TRACE_PLAN names the groups.
+ * Errors: a null cs / corpus / args / comparator / output, k == 0 or an f64-valued metric (jaro, jaro_winkler, fuzz ratio) is
+ * RF_ERR_INVALID_ARG -- decided before the corpus is looked at or a device is touched; q == 0 is RF_OK and writes nothing; an empty
+ * corpus is RF_OK with every count 0 (outputs other than out_count may then be NULL).  No error becomes an empty row.
+ * Out of scope: f64 scores (normalized_*, the f64 metrics: rf_topk_f64 per query), device-resident output, and a multi-GPU exchange
+ * for this call (shards merge on the host with rf_topk_merge_u32, row by row). */
+rf_status rf_topk_multi_u32(const rf_comparator *const *cs, uint32_t q, const rf_corpus *corpus, rf_op op,
+                            const rf_args *args, uint32_t k, uint64_t index_base,
+                            uint32_t *out_score, uint64_t *out_index, uint32_t *out_count, void *stream);
 
 /* ---- top-k ------------------------------------------------------------------------------------
  * The reference has no extract/top-k API; this is the engine's own reduction over the scores above,

@@ -113,7 +113,7 @@ static rf_status topk_core(const rf_comparator* c_in, const rf_corpus* corpus_in
     // tight cutoff (p.early) the cutoff itself keeps nearly everything out of the lists and the pass is skipped.
     // Each launch selects its own k best in its last workgroup (topk_block_publish): 2 launches, or 1.
     // (RF_TOPK_SAMPLE=<tiles> tunes the sample size, 0 disables the pass: A/B switch)
-    static const uint32_t kSampleTiles = (uint32_t)env_int("RF_TOPK_SAMPLE", 1024);
+    const uint32_t kSampleTiles = sw_topk_sample();
     if (kSampleTiles && !p.early && p.tile_end - p.tile_begin >= 8 * kSampleTiles) {
         ScanParams ps = p;
         ps.out = nullptr;

@@ -179,6 +179,21 @@ struct ScanParams {
     uint32_t topk_bound_from_result;  // sample pass: leave (k-th best key + 1) in *topk_bound for the main scan
 };
 
+// rf_topk_multi.hip: top-k for Q = 2 / 4 fused queries (rf_topk_multi_u32).  `s` is what scan_multi_kernel reads (corpus, finishing coefficients, multi_q /
+// multi_len1 / multi_pm) + tile_begin / tile_end / tile_step + topk_k / topk_desc; everything below is per-call scratch.
+constexpr uint32_t kTopkMultiLine64 = 16, kTopkMultiLine32 = 32;  // u64 / u32 units per 128-byte line: one bound, one counter per line
+struct TopkMultiParams {
+    ScanParams s;
+    uint64_t* bound;    // [Q] lines: the query's launch-wide upper bound on its k-th best key (~0: none yet)
+    uint32_t* count;    // [Q] lines: keys published to the query's segment (zero between launches)
+    uint64_t* cand;     // [Q][seg_cap] published keys: (score or ~score) << 32 | local index
+    uint32_t seg_cap;   // >= workgroups of the launch x topk_k
+    uint32_t sample;    // topk_multi_select_kernel: 1 = leave (k-th best key + 1) in the bounds instead of writing the keys
+};
+int topk_multi_grid(uint32_t tiles);  // workgroups of a launch_topk_multi over `tiles` tiles
+hipError_t launch_topk_multi(RawKind raw, bool narrow, const TopkMultiParams& tp, hipStream_t stream);
+hipError_t launch_topk_multi_select(const TopkMultiParams& tp, uint64_t* keys /*[Q][topk_k]*/, hipStream_t stream);
+
 // kernel launchers (rf_scan.hip, rf_long.hip, rf_damerau.hip, rf_jaro.hip, rf_pack.hip)
 hipError_t launch_scan(RawKind raw, const ScanParams& p, hipStream_t stream, int* grid_used);
 hipError_t launch_osa1_asm(const ScanParams& p, hipStream_t stream, int grid);   // the same around the OSA column (OsaState<1>)
@@ -318,6 +333,7 @@ inline bool sw_asm_chunk() { static const bool v = env_on("RF_ASM_CHUNK"); retur
 inline bool sw_jaro_priv() { static const bool v = env_int("RF_JARO_PRIV", 0) != 0; return v; }  // (off by default: rf_jaro.hip launch_jaro_word)
 inline bool sw_no_mixed_tiles() { static const bool v = env_set("RF_NO_MIXED_TILES"); return v; }
 inline bool sw_pack_timing() { static const bool v = env_set("RF_PACK_TIMING"); return v; }
+inline uint32_t sw_topk_sample() { static const uint32_t v = (uint32_t)env_int("RF_TOPK_SAMPLE", 1024); return v; }  // tiles of the top-k bound sample (rf_api_topk.hip, rf_api_topk_multi.hip)
 inline bool sw_trace_plan() { static const bool v = env_set("RF_TRACE_PLAN"); return v; }  // one line per call on stderr: which path the plan took
 inline bool sw_stream_timing() { static const bool v = env_set("RF_STREAM_TIMING"); return v; }  // phase times of a streamed scan on stderr
 #ifdef RF_EXPERIMENTS  // measurement builds only (tools/build_stream_variant.sh): the shipping library has no switch that changes a result
