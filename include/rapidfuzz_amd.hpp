@@ -6,6 +6,7 @@
 // (BatchComparator), src/fuzz.rs:48-150.  Every score is computed by the HIP kernels behind rfgpu.h.
 #pragma once
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <limits>
@@ -201,6 +202,21 @@ public:
         return topk_multi(scorers, c, k, RF_OP_SIMILARITY, a.to_c(), index_base);
     }
 
+    // ---- the candidates within the cutoff for every query, one call (rf_filter_multi_u32): res[j] = distance_filter_many of scorers[j] -- (index_base + index,
+    // score) pairs, in `order`.  Queries under a tight cutoff share passes over the corpus, 4 (or 2) to a pass; no [q][n] matrix is built.  usize metrics only.
+    static std::vector<std::vector<std::pair<uint64_t, size_t>>> distance_filter_multi(const std::vector<const BatchComparator*>& scorers, const Corpus& c,
+                                                                                        const Args<usize_result>& a = {}, rf_filter_order order = RF_FILTER_BY_INDEX,
+                                                                                        uint64_t index_base = 0)
+    {
+        return filter_multi(scorers, c, RF_OP_DISTANCE, a.to_c(), order, index_base);
+    }
+    static std::vector<std::vector<std::pair<uint64_t, size_t>>> similarity_filter_multi(const std::vector<const BatchComparator*>& scorers, const Corpus& c,
+                                                                                          const Args<usize_result>& a = {}, rf_filter_order order = RF_FILTER_BY_INDEX,
+                                                                                          uint64_t index_base = 0)
+    {
+        return filter_multi(scorers, c, RF_OP_SIMILARITY, a.to_c(), order, index_base);
+    }
+
     // ---- the reference's per-candidate methods (a one-candidate corpus through the same kernels)
     std::optional<usize_result> distance_with_args(std::string_view s2, const Args<usize_result>& a) const
     {
@@ -258,6 +274,28 @@ private:
         for (size_t j = 0; j < q; ++j)
             for (uint32_t m = 0; m < count[j]; ++m) res[j].emplace_back(index[j * k + m], (size_t)score[j * k + m]);
         return res;
+    }
+    static std::vector<std::vector<std::pair<uint64_t, size_t>>> filter_multi(const std::vector<const BatchComparator*>& scorers, const Corpus& c, rf_op op, const rf_args& a,
+                                                                              rf_filter_order order, uint64_t index_base)
+    {
+        static_assert(!FloatMetric, "rf_filter_multi_u32 serves the usize-valued metrics");
+        std::vector<const rf_comparator*> hs;
+        for (const BatchComparator* s : scorers) hs.push_back(s->h_);
+        const size_t q = hs.size();
+        if (q == 0) return {};  // (an empty vector has no data(): the C ABI refuses a null list even of no queries)
+        // (a first guess per row: fused rows sit under a tight cutoff and are short, and q rows of it are allocated here and on the device)
+        uint64_t cap = std::clamp<uint64_t>(c.size() / 4096, 64, 1u << 12);
+        for (;;) {  // (the device reports the true counts: at most one repeat, with room for the largest)
+            std::vector<uint64_t> index(q * cap), count(q);
+            std::vector<uint32_t> score(q * cap);
+            check(rf_filter_multi_u32(hs.data(), (uint32_t)q, c.handle(), op, &a, index_base, cap, index.data(), score.data(), count.data(), order, nullptr));
+            const uint64_t most = *std::max_element(count.begin(), count.end());
+            if (most > cap) { cap = most; continue; }
+            std::vector<std::vector<std::pair<uint64_t, size_t>>> res(q);
+            for (size_t j = 0; j < q; ++j)
+                for (uint64_t m = 0; m < count[j]; ++m) res[j].emplace_back(index[j * cap + m], (size_t)score[j * cap + m]);
+            return res;
+        }
     }
     template <class T>
     std::vector<std::pair<uint64_t, T>> filter(const Corpus& c, rf_op op, const rf_args& a, rf_filter_order order) const

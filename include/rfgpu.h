@@ -70,6 +70,7 @@
  *   RF_TOPK_VIA_SCORES            1         top-k (k <= 64) as scan + one pass over the scores: 0 never, 1 multi-word Levenshtein, 2 every shape with an asm scan
  *   RF_TOPK_SAMPLE                1024      tiles of the in-scan top-k's bound sample (0: no sample pass)
  *   RF_TOPK_MULTI                 1         0: rf_topk_multi_u32 sends every query through rf_topk_u32 instead of fusing 4 (or 2) to a pass over the corpus
+ *   RF_FILTER_MULTI               1         0: rf_filter_multi_u32 sends every query through rf_filter_u32 instead of fusing tight-cutoff queries 4 (or 2) to a pass over the corpus
  *   RF_JARO_PRIV                  0         1: Jaro asm kernel gathers from a conflict-free copy of the pattern table (corpora of <= 64 symbols; measured: no gain)
  *   RF_WF_REG                     1         0: LDS rows instead of register rows for generalized weights, queries <= 64
  *   RF_TRANSLATE_DIRECT           1         0: staged translation of u32 overflow symbols
@@ -405,6 +406,32 @@ rf_status rf_many_multi_f64(const rf_comparator *const *cs, uint32_t q, const rf
 rf_status rf_topk_multi_u32(const rf_comparator *const *cs, uint32_t q, const rf_corpus *corpus, rf_op op,
                             const rf_args *args, uint32_t k, uint64_t index_base,
                             uint32_t *out_score, uint64_t *out_index, uint32_t *out_count, void *stream);
+
+/* ---- the candidates within the cutoff for many queries x one corpus ---------------------------------
+ * Row j is exactly what rf_filter_u32(cs[j], corpus, op, args, index_base, capacity, ..., RF_MEM_HOST, order, stream) returns (see "filter"
+ * above), with the same `args` -- the same cutoff -- for every query as in rf_many_multi_*.  op is RF_OP_DISTANCE or RF_OP_SIMILARITY.
+ * Outputs are HOST arrays: out_index and out_score row-major [q][capacity], out_count[q].  out_count[j] is ALWAYS the true number of
+ * candidates whose result is not None; when it exceeds `capacity`, row j holds `capacity` of the qualifying pairs -- valid, distinct, in the
+ * requested order among themselves, not necessarily the first ones (the single-query call's contract, per row).  capacity == 0 is a pure
+ * count (the two row arrays may then be NULL).  Only the first min(out_count[j], capacity) entries of row j are defined.
+ * Queries whose cutoff is TIGHT (the planner's early-out rule: the ones a dense scan would answer None nearly everywhere) -- levenshtein
+ * (uniform or Indel-like weights) / indel / lcs_seq, <= 64 symbols -- are evaluated 4 (or 2) at a time by ONE pass over the corpus that
+ * drops a query from a tile as soon as none of the tile's 64 candidates can pass it any more and appends the passers to a compact list
+ * per query: no [q][n] matrix and no n-entry vector exists at any point, and the call brings everything home in one copy (two when the segments are large: the counts, then the filled part of all rows).  Every other
+ * query (no cutoff or a loose one, osa, damerau_levenshtein, general weight tables, longer queries, a u32 query with overflow-class
+ * symbols, the odd one left over, and levenshtein under a cutoff small enough for a first look at column 8 over a single-length corpus
+ * of 2^25 candidates or more, where the per-query head-plane scan measured faster than the fused pass) goes through rf_filter_u32
+ * itself, one call per query.  RF_TRACE_PLAN names the groups.
+ * Errors: a null cs / corpus / args / out_count / comparator, a null row array with capacity != 0, an unknown order, an op other than the
+ * two above or an f64-valued metric (jaro, jaro_winkler, fuzz ratio) is RF_ERR_INVALID_ARG -- decided before the corpus is looked at or a
+ * device is touched, and nothing is written; q == 0 is RF_OK and writes nothing; an empty corpus is RF_OK with every count 0.  No error
+ * becomes an empty row.
+ * Out of scope: f64 scores (normalized_*, the f64 metrics: rf_filter_f64 per query), device-resident output, and a multi-GPU form (shards
+ * are separate calls with their index_base; their rows concatenate). */
+rf_status rf_filter_multi_u32(const rf_comparator *const *cs, uint32_t q, const rf_corpus *corpus, rf_op op,
+                              const rf_args *args, uint64_t index_base, uint64_t capacity,
+                              uint64_t *out_index, uint32_t *out_score, uint64_t *out_count,
+                              rf_filter_order order, void *stream);
 
 /* ---- top-k ------------------------------------------------------------------------------------
  * The reference has no extract/top-k API; this is the engine's own reduction over the scores above,

@@ -239,6 +239,33 @@ class BatchComparator:
                 return idx[:m], sc[:m]
             cap = int(cnt.value)
 
+    @classmethod
+    def filter_multi(cls, comparators: Sequence["BatchComparator"], op: int, corpus: Corpus, args: Optional[Args] = None, capacity: Optional[int] = None,
+                     order: int = N.FILTER_BY_INDEX, index_base: int = 0, stream=None, *, score_cutoff=None, score_hint=None, weights=None, prefix_weight=None):
+        """[(indices uint64[m_j], scores uint32[m_j]) for every comparator]: pair j is `comparators[j].filter_many(op, corpus, ...)` (rf_filter_multi_u32) --
+        distance or similarity of the usize metrics, one cutoff for every query.  Queries of <= 64 symbols of one metric under a tight cutoff are fused 4 at a
+        time into one pass over the corpus that appends the matches to a compact list per query; no [q, n] matrix is built.  `capacity` bounds every
+        row; None = a default, then one repeat with room for the largest count if a row overflowed.  `last_filter_counts` (on the class the call was made
+        through) holds the true counts."""
+        a = _mk_args(args, score_cutoff, score_hint, weights, prefix_weight)
+        ca = a.to_c(False)
+        q = len(comparators)
+        if q == 0:
+            return []
+        hs = (C.c_void_p * q)(*[c._h for c in comparators])
+        # (a first guess per row: fused rows sit under a tight cutoff and are short, the counts that come back are true, and q rows of it are allocated)
+        cap = int(capacity) if capacity is not None else max(64, min(len(corpus) // 4096, 1 << 12))
+        while True:
+            idx = np.empty((q, max(cap, 1)), dtype=np.uint64)
+            sc = np.empty((q, max(cap, 1)), dtype=np.uint32)
+            cnt = np.zeros(q, dtype=np.uint64)
+            N.check(N.lib().rf_filter_multi_u32(hs, q, corpus._h, op, C.byref(ca), index_base, cap, idx.ctypes.data if cap else None, sc.ctypes.data if cap else None,
+                                                cnt.ctypes.data, order, stream))
+            if capacity is not None or int(cnt.max()) <= cap:
+                cls.last_filter_counts = [int(x) for x in cnt]
+                return [(idx[j, : min(int(cnt[j]), cap)].copy(), sc[j, : min(int(cnt[j]), cap)].copy()) for j in range(q)]
+            cap = int(cnt.max())
+
     def distance_many(self, corpus, args=None, **kw):
         return self.many(N.OP_DISTANCE, corpus, args, **kw)
 

@@ -1,0 +1,154 @@
+// rf_filter_multi.hip -- the candidates within a tight cutoff for Q queries in one pass over the corpus (rf_filter_multi_u32): topk_multi_kernel's
+// frame (Q tables side by side in LDS, one candidate per lane, Q recurrence states per lane) with scan_body's early-out schedule, and at a tile's
+// end one compact append per query that still has a passing lane.  Nothing is stored per candidate otherwise.
+// Product code: never includes or links anything from oracle/.
+#include <algorithm>
+
+#include "rf_internal.hpp"
+#include "rf_device.hpp"
+
+namespace rf {
+
+// ---------------------------------------------------------------------------------------------------
+// The launch walks tiles tile_begin + i * stride < tile_end: the union of the members' length windows (a member whose own window excludes a
+// tile's length fails its first look there -- or, at the latest, the final compare).
+// Early-out: `live` is the wavefront-uniform set of members some lane of which may still pass (may_pass() over State::bound(), padding lanes
+// excluded).  A full first chunk takes the first look after column 8 (bound_first), every chunk takes one at its end (bound); a member whose
+// ballot is empty is dropped for the rest of the tile -- a uniform branch: its recurrences are not issued any more -- and a tile no member
+// of which is live is abandoned.  Every look is value-preserving: what a member returns is decided by usize_value() at the tile's end.
+// Memory: scan_body's cutoff mode.  The NEXT TILE's first chunk is requested at the top of a tile; a wavefront that survives a chunk fetches
+// its own next chunk on demand; whatever way the tile ends, the next tile starts from the prefetched chunk.
+// Emission: per live member m = ballot(valid && keep); lane 0 adds popcount(m) to the member's counter, the passing lanes store their keys at
+// base + rank while that is below seg_cap.  The counter counts on beyond seg_cap: it is the true number of matches.  Under a tight cutoff
+// passers are rare, so the atomics are (the planner fuses p.early queries only).
+// ---------------------------------------------------------------------------------------------------
+template <class State, int Q, bool kUniform>
+__global__ __launch_bounds__(kWave* kWavesPerBlock) void filter_multi_kernel(const FilterMultiParams fp)
+{
+    using Word = typename State::Word;
+    static_assert(State::kWords == 1, "multi-query kernels are single-word");
+    static_assert(State::kCanPrune, "the fused cutoff scan needs a state with a bound");
+    const ScanParams& p = fp.s;
+    __shared__ Word lds_pm[Q][256];
+    for (int i = threadIdx.x; i < Q * 256; i += kWave * kWavesPerBlock) {
+        const int q = i / 256, c = i % 256;
+        lds_pm[q][p.sigma[c]] = (Word)p.multi_pm[q][c];  // single-word tables: row stride 1
+    }
+    __syncthreads();
+
+    const uint32_t lane = threadIdx.x & (kWave - 1);
+    const uint32_t wave = uniform(threadIdx.x / kWave);
+    const uint32_t stride = gridDim.x * kWavesPerBlock;
+    constexpr uint32_t kAll = (1u << Q) - 1u;
+
+    uint32_t t = p.tile_begin + blockIdx.x * kWavesPerBlock + wave;
+    if (t >= p.tile_end) return;
+    TileView cur_tile = load_tile<kUniform>(p, t);
+    uint4 cur = load_chunk(cur_tile.src + lane);  // (the packed buffer carries one chunk of tail padding: always readable)
+    while (true) {
+        const uint32_t t_next = t + stride;
+        const bool has_next = t_next < p.tile_end;
+        const TileView next_tile = load_tile<kUniform>(p, has_next ? t_next : t);
+        const uint4 ahead = load_chunk(next_tile.src + lane);
+        const uint32_t len2 = cur_tile.len;
+        const uint32_t slot = cur_tile.slot0 + lane;
+        uint32_t idx = slot;
+        if (!kUniform) idx = p.orig[slot];
+        const bool valid = kUniform ? slot < p.n : idx != kPad;
+
+        State st[Q];
+        TileFin fin[Q];
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            st[q].init();
+            fin[q] = tile_fin(p, p.multi_len1[q], len2);
+        }
+        uint32_t live = kAll;
+        const uint32_t nch = (len2 + kChunk - 1) / kChunk;
+        for (uint32_t c = 0; c < nch; ++c) {
+            const uint32_t cols = len2 - c * kChunk;
+            if (cols >= kChunk && c == 0) {
+#pragma unroll
+                for (int q = 0; q < Q; ++q) {
+                    if (!(live & (1u << q))) continue;
+                    process_chunk_full<State, 0, 8>(st[q], lds_pm[q], cur);
+                    if (__ballot(valid && may_pass(p, fin[q], st[q].bound_first(p.multi_len1[q], 8, len2))) == 0)
+                        live &= ~(1u << q);
+                    else
+                        process_chunk_full<State, 8, kChunk>(st[q], lds_pm[q], cur);
+                }
+            } else {
+#pragma unroll
+                for (int q = 0; q < Q; ++q) {
+                    if (!(live & (1u << q))) continue;
+                    if (cols >= kChunk)
+                        process_chunk_full<State>(st[q], lds_pm[q], cur);
+                    else
+                        process_chunk_tail<State>(st[q], lds_pm[q], cur, cols);
+                }
+            }
+            const uint32_t j = min(len2, (c + 1) * kChunk);
+#pragma unroll
+            for (int q = 0; q < Q; ++q)
+                if ((live & (1u << q)) && __ballot(valid && may_pass(p, fin[q], st[q].bound(p.multi_len1[q], j, len2))) == 0) live &= ~(1u << q);
+            if (!live) break;  // every member's wavefront is beyond the cutoff: stop reading this tile
+            if (c + 1 < nch) cur = load_chunk(cur_tile.src + (size_t)(c + 1) * kWave + lane);
+        }
+
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            if (!(live & (1u << q))) continue;
+            const uint32_t raw = st[q].result(p.multi_len1[q], len2);
+            bool keep;
+            const uint32_t v = usize_value(p, fin[q], raw, &keep);
+            const bool pass = valid && keep;
+            const uint64_t m = __ballot(pass);
+            if (m) {
+                uint32_t base = 0;
+                if (lane == 0) base = atomicAdd(fp.count + q * kFilterMultiLine32, (uint32_t)__popcll(m));
+                base = uniform(base);
+                const uint32_t at = base + (uint32_t)__popcll(m & ((1ull << lane) - 1));
+                if (pass && at < fp.seg_cap) fp.cand[(size_t)q * fp.seg_cap + at] = ((uint64_t)(p.topk_desc ? ~v : v) << 32) | idx;
+            }
+        }
+
+        if (!has_next) break;
+        cur = ahead;  // dead, empty or walked to its end: the next tile starts from the prefetched chunk
+        t = t_next;
+        cur_tile = next_tile;
+    }
+}
+
+template <class State, int Q>
+static hipError_t launch_filter_multi_q(const FilterMultiParams& fp, hipStream_t stream, int grid)
+{
+    const dim3 g(grid), b(kWave * kWavesPerBlock);
+    if (fp.s.tiles)
+        hipLaunchKernelGGL((filter_multi_kernel<State, Q, false>), g, b, 0, stream, fp);
+    else
+        hipLaunchKernelGGL((filter_multi_kernel<State, Q, true>), g, b, 0, stream, fp);
+    return hipGetLastError();
+}
+template <class State>
+static hipError_t launch_filter_multi_state(const FilterMultiParams& fp, hipStream_t stream, int grid)
+{
+    switch (fp.s.multi_q) {
+    case 2: return launch_filter_multi_q<State, 2>(fp, stream, grid);
+    case 4: return launch_filter_multi_q<State, 4>(fp, stream, grid);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+// raw: RAW_LEV or RAW_LCS; every query single-word; `narrow` = every query <= 32 symbols.  The grid is scan_grid()'s, as topk_multi_grid's is.
+hipError_t launch_filter_multi(RawKind raw, bool narrow, const FilterMultiParams& fp, hipStream_t stream)
+{
+    const ScanParams& p = fp.s;
+    if (!fp.count || (fp.seg_cap && !fp.cand) || p.tile_end > p.n_tiles) return hipErrorInvalidValue;
+    if (p.tile_end <= p.tile_begin) return hipSuccess;
+    const int grid = std::max(1, scan_grid(p.tile_end - p.tile_begin));
+    if (raw == RAW_LEV) return narrow ? launch_filter_multi_state<Lev32State>(fp, stream, grid) : launch_filter_multi_state<LevState<1>>(fp, stream, grid);
+    if (raw == RAW_LCS) return narrow ? launch_filter_multi_state<Lcs32State>(fp, stream, grid) : launch_filter_multi_state<LcsState<1>>(fp, stream, grid);
+    return hipErrorInvalidValue;
+}
+
+}  // namespace rf

@@ -21,7 +21,7 @@ pub fn release_caches() {
     // (always RF_OK)
     let _ = unsafe { sys::rf_release_caches() };
 }
-pub use metric::{Args, DistanceCutoff, Element, Error, NoScoreCutoff, SimilarityCutoff, TopK, WeightTable, WithScoreCutoff};
+pub use metric::{Args, DistanceCutoff, Element, Error, FilterOrder, NoScoreCutoff, SimilarityCutoff, TopK, WeightTable, WithScoreCutoff};
 
 /// `rapidfuzz::distance::*` -- one module per metric with a bit-parallel batch path.  Each has `BatchComparator<Elem1>` with the
 /// reference's eight methods (`distance`, `distance_with_args`, `similarity`, ..., `normalized_similarity_with_args`), the eight free

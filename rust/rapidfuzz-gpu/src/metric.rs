@@ -227,6 +227,19 @@ impl Element for char {
 /// k best candidates under (score, index); the engine's own reduction (the reference has no extract API).
 pub struct TopK { pub scores: Vec<u32>, pub indices: Vec<u64> }
 
+/// The order of the pairs a `*_filter_multi` call returns per row (rf_filter_order): ascending index, best score first with ties by index, or as they arrived.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum FilterOrder { ByIndex, ByScore, Any }
+impl FilterOrder {
+    pub(crate) fn lower(self) -> c_int {
+        match self {
+            FilterOrder::ByIndex => RF_FILTER_BY_INDEX,
+            FilterOrder::ByScore => RF_FILTER_BY_SCORE,
+            FilterOrder::Any => RF_FILTER_ANY,
+        }
+    }
+}
+
 pub(crate) fn many_u32(c: *const RfComparator, corpus: &crate::Corpus, op: c_int, a: &RfArgs) -> Result<Vec<Option<usize>>, Error> {
     let mut out = vec![0u32; corpus.len()];
     check(unsafe { rf_many_u32(c, corpus.0, op, a, out.as_mut_ptr(), RF_MEM_HOST, std::ptr::null_mut()) })?;
@@ -251,6 +264,24 @@ pub(crate) fn filter_u32(c: *const RfComparator, corpus: &crate::Corpus, op: c_i
             return Ok(idx.into_iter().zip(val).take(n as usize).map(|(i, v)| (i, v as usize)).collect());
         }
         cap = n;
+    }
+}
+/// `filter_u32` for a list of comparators in one call (rf_filter_multi_u32): row j is `filter_u32(cs[j], ...)`; queries under a tight cutoff share
+/// passes over the corpus, 4 (or 2) to a pass.  One repeat with room for the largest count when a row overflowed.
+pub(crate) fn filter_multi_u32(cs: &[*const RfComparator], corpus: &crate::Corpus, op: c_int, a: &RfArgs, order: c_int, index_base: u64) -> Result<Vec<Vec<(u64, usize)>>, Error> {
+    if cs.is_empty() {
+        return Ok(Vec::new());
+    }
+    let q = cs.len();
+    let mut cap = (corpus.len() / 4096).clamp(64, 1 << 12) as u64;  // (per row, q rows of it: rows under a tight cutoff are short)
+    loop {
+        let (mut idx, mut val, mut n) = (vec![0u64; q * cap as usize], vec![0u32; q * cap as usize], vec![0u64; q]);
+        check(unsafe { rf_filter_multi_u32(cs.as_ptr(), q as u32, corpus.0, op, a, index_base, cap, idx.as_mut_ptr(), val.as_mut_ptr(), n.as_mut_ptr(), order, std::ptr::null_mut()) })?;
+        let most = n.iter().copied().max().unwrap_or(0);
+        if most <= cap {
+            return Ok((0..q).map(|j| (0..n[j] as usize).map(|m| (idx[j * cap as usize + m], val[j * cap as usize + m] as usize)).collect()).collect());
+        }
+        cap = most;
     }
 }
 pub(crate) fn filter_f64(c: *const RfComparator, corpus: &crate::Corpus, op: c_int, a: &RfArgs, order: c_int) -> Result<Vec<(u64, f64)>, Error> {
@@ -390,6 +421,16 @@ macro_rules! usize_metric {
                 /// ... and as (index, normalized similarity) pairs, best first.
                 pub fn normalized_similarity_filter_many<C: SimilarityCutoff<f64>>(&self, corpus: &Corpus, args: &Args<f64, C>) -> Result<Vec<(u64, f64)>, Error> {
                     filter_f64(self.h, corpus, RF_OP_NORMALIZED_SIMILARITY, &args.lower(args.score_cutoff.cutoff()), RF_FILTER_BY_SCORE)
+                }
+                /// `distance_filter_many` of every scorer in one call (rf_filter_multi_u32): row j belongs to `scorers[j]`; `index_base` as in `topk`.
+                pub fn distance_filter_multi<C: DistanceCutoff<usize>>(scorers: &[&Self], corpus: &Corpus, args: &Args<usize, C>, order: FilterOrder, index_base: u64) -> Result<Vec<Vec<(u64, usize)>>, Error> {
+                    let hs: Vec<*const RfComparator> = scorers.iter().map(|s| s.h as *const RfComparator).collect();
+                    filter_multi_u32(&hs, corpus, RF_OP_DISTANCE, &args.lower(args.score_cutoff.cutoff()), order.lower(), index_base)
+                }
+                /// ... and by similarity (at least the cutoff).
+                pub fn similarity_filter_multi<C: SimilarityCutoff<usize>>(scorers: &[&Self], corpus: &Corpus, args: &Args<usize, C>, order: FilterOrder, index_base: u64) -> Result<Vec<Vec<(u64, usize)>>, Error> {
+                    let hs: Vec<*const RfComparator> = scorers.iter().map(|s| s.h as *const RfComparator).collect();
+                    filter_multi_u32(&hs, corpus, RF_OP_SIMILARITY, &args.lower(args.score_cutoff.cutoff()), order.lower(), index_base)
                 }
                 /// k best candidates by (distance, index); `index_base` makes shards of one logical corpus comparable.
                 pub fn topk<C: DistanceCutoff<usize>>(&self, corpus: &Corpus, k: u32, args: &Args<usize, C>, index_base: u64) -> Result<TopK, Error> {
