@@ -202,6 +202,19 @@ public:
         return topk_multi(scorers, c, k, RF_OP_SIMILARITY, a.to_c(), index_base);
     }
 
+    // ---- the same for the f64-valued scores (rf_topk_multi_f64): res[j] = (index_base + index, score) pairs, normalized distance ascending / normalized
+    // similarity descending, ties by index; bit for bit the doubles normalized_*_many returns.  Fusable queries (see rfgpu.h) share passes over the corpus.
+    static std::vector<std::vector<std::pair<uint64_t, double>>> normalized_distance_topk_multi(const std::vector<const BatchComparator*>& scorers, const Corpus& c, uint32_t k,
+                                                                                                 const Args<double>& a = {}, uint64_t index_base = 0)
+    {
+        return topk_multi_f64(scorers, c, k, RF_OP_NORMALIZED_DISTANCE, a.to_c(), index_base);
+    }
+    static std::vector<std::vector<std::pair<uint64_t, double>>> normalized_similarity_topk_multi(const std::vector<const BatchComparator*>& scorers, const Corpus& c, uint32_t k,
+                                                                                                   const Args<double>& a = {}, uint64_t index_base = 0)
+    {
+        return topk_multi_f64(scorers, c, k, RF_OP_NORMALIZED_SIMILARITY, a.to_c(), index_base);
+    }
+
     // ---- the candidates within the cutoff for every query, one call (rf_filter_multi_u32): res[j] = distance_filter_many of scorers[j] -- (index_base + index,
     // score) pairs, in `order`.  Queries under a tight cutoff share passes over the corpus, 4 (or 2) to a pass; no [q][n] matrix is built.  usize metrics only.
     static std::vector<std::vector<std::pair<uint64_t, size_t>>> distance_filter_multi(const std::vector<const BatchComparator*>& scorers, const Corpus& c,
@@ -273,6 +286,22 @@ private:
         std::vector<std::vector<std::pair<uint64_t, size_t>>> res(q);
         for (size_t j = 0; j < q; ++j)
             for (uint32_t m = 0; m < count[j]; ++m) res[j].emplace_back(index[j * k + m], (size_t)score[j * k + m]);
+        return res;
+    }
+    static std::vector<std::vector<std::pair<uint64_t, double>>> topk_multi_f64(const std::vector<const BatchComparator*>& scorers, const Corpus& c, uint32_t k, rf_op op,
+                                                                                const rf_args& a, uint64_t index_base)
+    {
+        std::vector<const rf_comparator*> hs;
+        for (const BatchComparator* s : scorers) hs.push_back(s->h_);
+        const size_t q = hs.size();
+        if (q == 0) return {};  // (an empty vector has no data(): the C ABI refuses a null list even of no queries)
+        std::vector<double> score(q * k);
+        std::vector<uint32_t> count(q);
+        std::vector<uint64_t> index(q * k);
+        check(rf_topk_multi_f64(hs.data(), (uint32_t)q, c.handle(), op, &a, k, index_base, score.data(), index.data(), count.data(), nullptr));
+        std::vector<std::vector<std::pair<uint64_t, double>>> res(q);
+        for (size_t j = 0; j < q; ++j)
+            for (uint32_t m = 0; m < count[j]; ++m) res[j].emplace_back(index[j * k + m], score[j * k + m]);
         return res;
     }
     static std::vector<std::vector<std::pair<uint64_t, size_t>>> filter_multi(const std::vector<const BatchComparator*>& scorers, const Corpus& c, rf_op op, const rf_args& a,
@@ -363,6 +392,14 @@ public:
         return c_.similarity_many(c, a);
     }
     double similarity(std::string_view s2) const { return *c_.similarity_with_args(s2, {}); }
+    /// the k best candidates of every scorer, one call (rf_topk_multi_f64): (index_base + index, ratio) pairs, ratio descending, ties by index
+    static std::vector<std::vector<std::pair<uint64_t, double>>> similarity_topk_multi(const std::vector<const RatioBatchComparator*>& scorers, const Corpus& c, uint32_t k,
+                                                                                        const detail::Args<double>& a = {}, uint64_t index_base = 0)
+    {
+        std::vector<const detail::BatchComparator<RF_FUZZ_RATIO, true>*> inner;
+        for (const RatioBatchComparator* s : scorers) inner.push_back(&s->c_);
+        return detail::BatchComparator<RF_FUZZ_RATIO, true>::normalized_similarity_topk_multi(inner, c, k, a, index_base);
+    }
 
 private:
     detail::BatchComparator<RF_FUZZ_RATIO, true> c_;

@@ -69,7 +69,7 @@
  *   RF_GATHER_SPAN / RF_GATHER_UNROLL   16384 / 8   window gather tuning
  *   RF_TOPK_VIA_SCORES            1         top-k (k <= 64) as scan + one pass over the scores: 0 never, 1 multi-word Levenshtein, 2 every shape with an asm scan
  *   RF_TOPK_SAMPLE                1024      tiles of the in-scan top-k's bound sample (0: no sample pass)
- *   RF_TOPK_MULTI                 1         0: rf_topk_multi_u32 sends every query through rf_topk_u32 instead of fusing 4 (or 2) to a pass over the corpus
+ *   RF_TOPK_MULTI                 1         0: rf_topk_multi_u32 / _f64 send every query through rf_topk_u32 / _f64 instead of fusing 4 (or 2) to a pass over the corpus
  *   RF_FILTER_MULTI               1         0: rf_filter_multi_u32 sends every query through rf_filter_u32 instead of fusing tight-cutoff queries 4 (or 2) to a pass over the corpus
  *   RF_JARO_PRIV                  0         1: Jaro asm kernel gathers from a conflict-free copy of the pattern table (corpora of <= 64 symbols; measured: no gain)
  *   RF_WF_REG                     1         0: LDS rows instead of register rows for generalized weights, queries <= 64
@@ -401,11 +401,34 @@ rf_status rf_many_multi_f64(const rf_comparator *const *cs, uint32_t q, const rf
  * Errors: a null cs / corpus / args / comparator / output, k == 0 or an f64-valued metric (jaro, jaro_winkler, fuzz ratio) is
  * RF_ERR_INVALID_ARG -- decided before the corpus is looked at or a device is touched; q == 0 is RF_OK and writes nothing; an empty
  * corpus is RF_OK with every count 0 (outputs other than out_count may then be NULL).  No error becomes an empty row.
- * Out of scope: f64 scores (normalized_*, the f64 metrics: rf_topk_f64 per query), device-resident output, and a multi-GPU exchange
+ * Out of scope: f64 scores (normalized_*, the f64 metrics: rf_topk_multi_f64 below), device-resident output, and a multi-GPU exchange
  * for this call (shards merge on the host with rf_topk_merge_u32, row by row). */
 rf_status rf_topk_multi_u32(const rf_comparator *const *cs, uint32_t q, const rf_corpus *corpus, rf_op op,
                             const rf_args *args, uint32_t k, uint64_t index_base,
                             uint32_t *out_score, uint64_t *out_index, uint32_t *out_count, void *stream);
+
+/* ---- top-k of f64 scores for many queries x one corpus ----------------------------------------------
+ * Row j is exactly what rf_topk_f64(cs[j], corpus, op, args, k, index_base, ...) returns: the same values bit for bit, the same
+ * (score, index) order, the same index_base, the same None rule under args->cutoff_f64, any k >= 1.  Every (comparator, op) pair
+ * rf_topk_f64 accepts is accepted: RF_OP_NORMALIZED_DISTANCE / RF_OP_NORMALIZED_SIMILARITY of the usize metrics, fuzz ratio with its
+ * similarity ops (and RF_FLAG_RATIO_INDEL_NORMALIZATION), every op of jaro / jaro_winkler.  Outputs are HOST arrays as in
+ * rf_topk_multi_u32, out_score holding doubles.
+ * Fused 4 (or 2) to a pass over the corpus, under rf_topk_multi_u32's grouping rules: levenshtein (uniform or Indel-like weights) /
+ * indel / lcs_seq / fuzz ratio queries of <= 64 symbols, no tight cutoff, k <= 64, whose largest possible maximum over this corpus is
+ * <= 65535 -- the in-scan lists order by an exact 32-bit image of dist / maximum (floor(dist * 2^32 / maximum)) that exists up to
+ * there; the host turns it back into the very double rf_topk_f64 returns.  Every other query (jaro, jaro_winkler, osa,
+ * damerau_levenshtein, general weight tables, longer queries, a tight cutoff, a u32 query with overflow-class symbols, a maximum
+ * beyond 65535, the odd one left over, every query when k > 64) goes through rf_topk_f64 itself, one call per query.  RF_TRACE_PLAN
+ * names the groups; RF_TOPK_MULTI=0 sends every query per query.
+ * Errors: a null cs / corpus / args / comparator / output, k == 0, RF_OP_DISTANCE / RF_OP_SIMILARITY of a usize metric (u32-valued:
+ * rf_topk_multi_u32) or a distance op of fuzz ratio is RF_ERR_INVALID_ARG -- decided before the corpus is looked at or a device is
+ * touched; q == 0 is RF_OK and writes nothing; an empty corpus is RF_OK with every count 0 (outputs other than out_count may then be
+ * NULL).  No error becomes an empty row.
+ * Out of scope: a thresholded form (rf_filter_f64 per query), device-resident output, and a multi-GPU exchange for this call (shards
+ * merge on the host, row by row). */
+rf_status rf_topk_multi_f64(const rf_comparator *const *cs, uint32_t q, const rf_corpus *corpus, rf_op op,
+                            const rf_args *args, uint32_t k, uint64_t index_base,
+                            double *out_score, uint64_t *out_index, uint32_t *out_count, void *stream);
 
 /* ---- the candidates within the cutoff for many queries x one corpus ---------------------------------
  * Row j is exactly what rf_filter_u32(cs[j], corpus, op, args, index_base, capacity, ..., RF_MEM_HOST, order, stream) returns (see "filter"

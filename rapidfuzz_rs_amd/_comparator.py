@@ -311,19 +311,22 @@ class BatchComparator:
     @classmethod
     def topk_multi(cls, comparators: Sequence["BatchComparator"], corpus: Corpus, k: int, op: Optional[int] = None, args: Optional[Args] = None,
                    index_base: int = 0, stream=None, *, score_cutoff=None, score_hint=None, weights=None, prefix_weight=None):
-        """[(scores[m_j], indices uint64[m_j]) for every comparator]: pair j is `comparators[j].topk(corpus, k, op, ...)` (rf_topk_multi_u32) --
-        uint32 scores, distance (the default) or similarity of the usize metrics.  Queries of <= 64 symbols of one metric are fused 4 at a
-        time into one pass over the corpus that returns k entries per query; no [q, n] matrix is built."""
+        """[(scores[m_j], indices uint64[m_j]) for every comparator]: pair j is `comparators[j].topk(corpus, k, op, ...)` -- uint32 scores for
+        distance (the default) or similarity of the usize metrics (rf_topk_multi_u32), float64 scores for normalized_* and for the float
+        classes (jaro, jaro_winkler, ratio: similarity is their default), rf_topk_multi_f64.  Queries of <= 64 symbols of one metric are fused
+        4 at a time into one pass over the corpus that returns k entries per query; no [q, n] matrix is built."""
+        is_f = cls.FLOAT or (op is not None and op >= N.OP_NORMALIZED_DISTANCE)
         if op is None:
-            op = N.OP_DISTANCE
+            op = N.OP_SIMILARITY if cls.FLOAT else N.OP_DISTANCE
         a = _mk_args(args, score_cutoff, score_hint, weights, prefix_weight)
-        ca = a.to_c(False)
+        ca = a.to_c(is_f)
         q = len(comparators)
         hs = (C.c_void_p * max(q, 1))(*[c._h for c in comparators])
-        scores = np.empty((q, k), dtype=np.uint32)
+        scores = np.empty((q, k), dtype=np.float64 if is_f else np.uint32)
         idx = np.empty((q, k), dtype=np.uint64)
         cnt = np.zeros(max(q, 1), dtype=np.uint32)
-        N.check(N.lib().rf_topk_multi_u32(hs, q, corpus._h, op, C.byref(ca), k, index_base, scores.ctypes.data, idx.ctypes.data, cnt.ctypes.data, stream))
+        fn = N.lib().rf_topk_multi_f64 if is_f else N.lib().rf_topk_multi_u32
+        N.check(fn(hs, q, corpus._h, op, C.byref(ca), k, index_base, scores.ctypes.data, idx.ctypes.data, cnt.ctypes.data, stream))
         return [(scores[j, : cnt[j]].copy(), idx[j, : cnt[j]].copy()) for j in range(q)]
 
     def topk_keys_device(self, corpus: Corpus, k: int, keys_out, op: int = N.OP_DISTANCE, args: Optional[Args] = None,

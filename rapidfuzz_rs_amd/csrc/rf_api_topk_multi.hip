@@ -1,12 +1,146 @@
-// rf_api_topk_multi.hip -- rf_topk_multi_u32: the k best candidates of each of q queries, fusable queries 4 (then 2) to a pass over the
-// corpus (rf_topk_multi.hip), every other query through rf_topk_u32 (rf_host.hpp has the shared declarations).
+// rf_api_topk_multi.hip -- rf_topk_multi_u32 / rf_topk_multi_f64: the k best candidates of each of q queries, fusable queries 4 (then 2) to
+// a pass over the corpus (rf_topk_multi.hip), every other query through rf_topk_u32 / rf_topk_f64 (rf_host.hpp has the shared declarations).
 // Product code: never includes or links anything from oracle/.
 #include "rf_host.hpp"
+
+#include "rf_norm_key.hpp"
 
 extern "C" {
 
 // A/B switch: 0 sends every query down the per-query road (identical results)
 static bool sw_topk_multi() { static const bool v = env_on("RF_TOPK_MULTI"); return v; }
+
+// What rf_topk_multi_u32 and rf_topk_multi_f64 share, after their argument checks: plan every query, group the fusable ones, run the groups
+// and bring their keys home.  `norm` (rf_topk_multi_f64): f64-valued plans, the normalized kernels, and one more condition on a fusable
+// query -- the largest maximum it can meet in this corpus fits the 32-bit score image.
+struct FusedTopk {
+    std::vector<std::vector<uint32_t>> groups;  // members of each fused group, as indices into cs
+    std::vector<char> taken;                    // [q] 1: the query is in a group
+    std::vector<uint64_t> keys;                 // [fused rows in group order][k], best first, ~0 = empty
+};
+static rf_status topk_multi_fused(bool norm, const rf_comparator* const* cs, uint32_t q, const rf_corpus* corpus, rf_op op, const rf_args* args, uint32_t k,
+                                  hipStream_t st, FusedTopk* out)
+{
+    // ---- plan every query; which ones can be fused
+    std::vector<ScanParams> ps(q);
+    std::vector<RawKind> raws(q, RAW_LEV);
+    std::vector<const rf_comparator*> eff(q, nullptr);
+    std::vector<ComparatorRef> holds(q);
+    std::vector<char> fusable(q, 0);
+    if (sw_topk_multi() && k <= (uint32_t)kWave)
+        for (uint32_t i = 0; i < q; ++i) {
+            // (a query that does not resolve -- overflow-class symbols need a translated image of the corpus -- or does not plan goes to
+            // the single-query call, which serves it or reports why not)
+            if (resolve(cs[i], corpus, &eff[i], &holds[i]) != RF_OK) continue;
+            if (plan(eff[i], corpus, op, args, norm, &ps[i], &raws[i]) != RF_OK) continue;
+            fusable[i] = (raws[i] == RAW_LEV || raws[i] == RAW_LCS) && eff[i]->words == 1 && !ps[i].long_words_pad && !ps[i].early;
+            if (norm && fusable[i]) {
+                // the 32-bit score image (rf_norm_key.hpp) is exact while every maximum of the scan is <= 65535; the maximum grows with the candidate's length
+                const uint64_t len1 = ps[i].len1, len2 = corpus->max_len;
+                const uint64_t largest = (uint64_t)ps[i].fin_mS * (len1 + len2) + (uint64_t)ps[i].fin_mM * std::max(len1, len2);
+                fusable[i] = largest <= kNormKeyMaxMaximum;
+            }
+        }
+    // (ps[].op: what the kernel computes -- a fuzz ratio plans to RF_OP_NORMALIZED_SIMILARITY whichever similarity op was asked for)
+    auto same_group = [&](uint32_t a, uint32_t b) {
+        return raws[a] == raws[b] && ps[a].finish == ps[b].finish && ps[a].factor == ps[b].factor && ps[a].op == ps[b].op &&
+               (ps[a].len1 <= 32) == (ps[b].len1 <= 32);
+    };
+    // (rows are independent here, so unlike run_many_multi's a group's members need not be neighbours)
+    std::vector<std::vector<uint32_t>>& groups = out->groups;
+    std::vector<char>& taken = out->taken;
+    taken.assign(q, 0);
+    for (uint32_t i = 0; i < q; ++i) {
+        if (taken[i] || !fusable[i]) continue;
+        std::vector<uint32_t> g{i};
+        for (uint32_t j = i + 1; j < q && g.size() < (size_t)kMaxMulti; ++j)
+            if (!taken[j] && fusable[j] && same_group(i, j)) g.push_back(j);
+        if (g.size() == 3) g.pop_back();
+        if (g.size() < 2) continue;  // the odd one left over
+        for (uint32_t m : g) taken[m] = 1;
+        groups.push_back(std::move(g));
+    }
+    uint32_t fused = 0;
+    for (const auto& g : groups) fused += (uint32_t)g.size();
+    const uint32_t n_tiles = corpus->n_tiles;
+    const uint32_t sample_tiles = sw_topk_sample();
+    const bool sample = !groups.empty() && sample_tiles && n_tiles >= 8 * sample_tiles;  // topk_core's rule (a fused group never has a tight cutoff)
+    if (sw_trace_plan()) {
+        std::string sizes;
+        for (const auto& g : groups) sizes += (sizes.empty() ? "" : ",") + std::to_string(g.size());
+        std::fprintf(stderr, "[rf plan] %s: q=%u k=%u fused_groups=[%s] per_query=%u sample=%d\n", norm ? "topk_multi_f64" : "topk_multi", q, k, sizes.c_str(), q - fused, sample ? 1 : 0);
+    }
+
+    // ---- the fused groups: everything enqueued, one copy home
+    std::vector<uint64_t>& keys = out->keys;
+    keys.assign((size_t)fused * k, ~0ull);
+    hipError_t e = hipSuccess;
+    rf_status status = RF_OK;
+    if (fused) {
+        DeviceGuard guard(corpus->device);
+        if (!guard.ok) {
+            set_error("cannot select the corpus' device");
+            return RF_ERR_NO_DEVICE;
+        }
+        ScratchSet sc(st);
+        // One group's scratch, reused by the next (stream order): [kMaxMulti bound lines | kMaxMulti counter lines | kMaxMulti segments], and the
+        // keys of every group.  A segment holds a full k-entry list from every workgroup of the larger launch (rf_topk_multi.hip topk_multi_grid:
+        // at most 32 workgroups per CU, 4 MiB per query at k = 64 on 256 CUs).
+        const uint32_t grid_main = (uint32_t)topk_multi_grid(n_tiles);
+        const uint32_t seg_cap = grid_main * k;  // (the sample's grid is never larger)
+        const size_t ctl_bytes = 2 * (size_t)kMaxMulti * 128;
+        uint8_t* ctl = nullptr;
+        uint64_t *cand = nullptr, *d_keys = nullptr;
+        RF_HIP(sc.get(&ctl, ctl_bytes));
+        RF_HIP(sc.get(&cand, (size_t)kMaxMulti * seg_cap * sizeof(uint64_t)));
+        RF_HIP(sc.get(&d_keys, keys.size() * sizeof(uint64_t)));
+        uint32_t row = 0;
+        for (const auto& g : groups) {
+            const uint32_t i = g[0];
+            TopkMultiParams tp{};
+            tp.s = ps[i];
+            ScanParams& p = tp.s;
+            p.out = nullptr, p.early = 0, p.prefill_none = 0;
+            p.tile_begin = 0, p.tile_end = n_tiles, p.tile_step = 1;
+            p.multi_q = (uint32_t)g.size();
+            p.topk_k = k;
+            p.topk_desc = op == RF_OP_SIMILARITY;  // (not read under norm: both normalized ops order by ascending norm_key)
+            tp.norm = norm ? 1u : 0u;
+            p.key_index_base = 0;  // index_base is added on the host, in 64 bits
+            for (size_t m = 0; m < g.size() && status == RF_OK; ++m) {
+                p.multi_len1[m] = ps[g[m]].len1;
+                status = comparator_device_pm(eff[g[m]], corpus->device, &p.multi_pm[m]);
+            }
+            if (status != RF_OK) break;
+            tp.bound = reinterpret_cast<uint64_t*>(ctl);
+            tp.count = reinterpret_cast<uint32_t*>(ctl + (size_t)kMaxMulti * 128);
+            tp.cand = cand;
+            tp.seg_cap = seg_cap;
+            e = hipMemsetAsync(tp.bound, 0xFF, (size_t)kMaxMulti * 128, st);
+            if (e == hipSuccess) e = hipMemsetAsync(tp.count, 0, (size_t)kMaxMulti * 128, st);
+            const bool narrow = p.len1 <= 32;
+            if (e == hipSuccess && sample) {
+                TopkMultiParams ts = tp;
+                ts.s.tile_step = n_tiles / sample_tiles;
+                ts.sample = 1;
+                e = launch_topk_multi(raws[i], narrow, ts, st);
+                if (e == hipSuccess) e = launch_topk_multi_select(ts, nullptr, st);
+            }
+            if (e == hipSuccess) e = launch_topk_multi(raws[i], narrow, tp, st);
+            if (e == hipSuccess) e = launch_topk_multi_select(tp, d_keys + (size_t)row * k, st);
+            if (e != hipSuccess) break;
+            row += (uint32_t)g.size();
+        }
+        if (status == RF_OK && e == hipSuccess) e = copy_home(keys.data(), d_keys, keys.size() * sizeof(uint64_t), st);
+        else (void)hipStreamSynchronize(st);
+        if (status != RF_OK) return status;
+        if (e != hipSuccess) {
+            set_error(std::string("top-k, fused queries: ") + hipGetErrorString(e));
+            return e == hipErrorOutOfMemory ? RF_ERR_OOM : RF_ERR_HIP;
+        }
+    }
+    return RF_OK;
+}
 
 // Row j is rf_topk_u32(cs[j], ...).  Queries are planned as run_many_multi plans them and fused under its rules -- single-word Levenshtein /
 // LCS-family recurrences that agree on the kernel family, finishing, factor and word width, no long pattern, no tight cutoff (a head-plane
@@ -53,115 +187,11 @@ try {
     if (corpus->n == 0) return RF_OK;
     const rf_args args_v = sanitized_args(args_in, false), *args = &args_v;
 
-    // ---- plan every query; which ones can be fused
-    std::vector<ScanParams> ps(q);
-    std::vector<RawKind> raws(q, RAW_LEV);
-    std::vector<const rf_comparator*> eff(q, nullptr);
-    std::vector<ComparatorRef> holds(q);
-    std::vector<char> fusable(q, 0);
-    if (sw_topk_multi() && k <= (uint32_t)kWave)
-        for (uint32_t i = 0; i < q; ++i) {
-            // (a query that does not resolve -- overflow-class symbols need a translated image of the corpus -- or does not plan goes to
-            // rf_topk_u32, which serves it or reports why not)
-            if (resolve(cs[i], corpus, &eff[i], &holds[i]) != RF_OK) continue;
-            if (plan(eff[i], corpus, op, args, false, &ps[i], &raws[i]) != RF_OK) continue;
-            fusable[i] = (raws[i] == RAW_LEV || raws[i] == RAW_LCS) && eff[i]->words == 1 && !ps[i].long_words_pad && !ps[i].early;
-        }
-    auto same_group = [&](uint32_t a, uint32_t b) {
-        return raws[a] == raws[b] && ps[a].finish == ps[b].finish && ps[a].factor == ps[b].factor && ps[a].op == ps[b].op &&
-               (ps[a].len1 <= 32) == (ps[b].len1 <= 32);
-    };
-    // (rows are independent here, so unlike run_many_multi's a group's members need not be neighbours)
-    std::vector<std::vector<uint32_t>> groups;
-    std::vector<char> taken(q, 0);
-    for (uint32_t i = 0; i < q; ++i) {
-        if (taken[i] || !fusable[i]) continue;
-        std::vector<uint32_t> g{i};
-        for (uint32_t j = i + 1; j < q && g.size() < (size_t)kMaxMulti; ++j)
-            if (!taken[j] && fusable[j] && same_group(i, j)) g.push_back(j);
-        if (g.size() == 3) g.pop_back();
-        if (g.size() < 2) continue;  // the odd one left over
-        for (uint32_t m : g) taken[m] = 1;
-        groups.push_back(std::move(g));
-    }
-    uint32_t fused = 0;
-    for (const auto& g : groups) fused += (uint32_t)g.size();
-    const uint32_t n_tiles = corpus->n_tiles;
-    const uint32_t sample_tiles = sw_topk_sample();
-    const bool sample = !groups.empty() && sample_tiles && n_tiles >= 8 * sample_tiles;  // topk_core's rule (a fused group never has a tight cutoff)
-    if (sw_trace_plan()) {
-        std::string sizes;
-        for (const auto& g : groups) sizes += (sizes.empty() ? "" : ",") + std::to_string(g.size());
-        std::fprintf(stderr, "[rf plan] topk_multi: q=%u k=%u fused_groups=[%s] per_query=%u sample=%d\n", q, k, sizes.c_str(), q - fused, sample ? 1 : 0);
-    }
-
-    // ---- the fused groups: everything enqueued, one copy home
-    hipStream_t st = (hipStream_t)stream;
-    std::vector<uint64_t> keys((size_t)fused * k, ~0ull);
-    hipError_t e = hipSuccess;
-    rf_status status = RF_OK;
-    if (fused) {
-        DeviceGuard guard(corpus->device);
-        if (!guard.ok) {
-            set_error("cannot select the corpus' device");
-            return RF_ERR_NO_DEVICE;
-        }
-        ScratchSet sc(st);
-        // One group's scratch, reused by the next (stream order): [kMaxMulti bound lines | kMaxMulti counter lines | kMaxMulti segments], and the
-        // keys of every group.  A segment holds a full k-entry list from every workgroup of the larger launch (rf_topk_multi.hip topk_multi_grid:
-        // at most 32 workgroups per CU, 4 MiB per query at k = 64 on 256 CUs).
-        const uint32_t grid_main = (uint32_t)topk_multi_grid(n_tiles);
-        const uint32_t seg_cap = grid_main * k;  // (the sample's grid is never larger)
-        const size_t ctl_bytes = 2 * (size_t)kMaxMulti * 128;
-        uint8_t* ctl = nullptr;
-        uint64_t *cand = nullptr, *d_keys = nullptr;
-        RF_HIP(sc.get(&ctl, ctl_bytes));
-        RF_HIP(sc.get(&cand, (size_t)kMaxMulti * seg_cap * sizeof(uint64_t)));
-        RF_HIP(sc.get(&d_keys, keys.size() * sizeof(uint64_t)));
-        uint32_t row = 0;
-        for (const auto& g : groups) {
-            const uint32_t i = g[0];
-            TopkMultiParams tp{};
-            tp.s = ps[i];
-            ScanParams& p = tp.s;
-            p.out = nullptr, p.early = 0, p.prefill_none = 0;
-            p.tile_begin = 0, p.tile_end = n_tiles, p.tile_step = 1;
-            p.multi_q = (uint32_t)g.size();
-            p.topk_k = k;
-            p.topk_desc = op == RF_OP_SIMILARITY;
-            p.key_index_base = 0;  // index_base is added on the host, in 64 bits
-            for (size_t m = 0; m < g.size() && status == RF_OK; ++m) {
-                p.multi_len1[m] = ps[g[m]].len1;
-                status = comparator_device_pm(eff[g[m]], corpus->device, &p.multi_pm[m]);
-            }
-            if (status != RF_OK) break;
-            tp.bound = reinterpret_cast<uint64_t*>(ctl);
-            tp.count = reinterpret_cast<uint32_t*>(ctl + (size_t)kMaxMulti * 128);
-            tp.cand = cand;
-            tp.seg_cap = seg_cap;
-            e = hipMemsetAsync(tp.bound, 0xFF, (size_t)kMaxMulti * 128, st);
-            if (e == hipSuccess) e = hipMemsetAsync(tp.count, 0, (size_t)kMaxMulti * 128, st);
-            const bool narrow = p.len1 <= 32;
-            if (e == hipSuccess && sample) {
-                TopkMultiParams ts = tp;
-                ts.s.tile_step = n_tiles / sample_tiles;
-                ts.sample = 1;
-                e = launch_topk_multi(raws[i], narrow, ts, st);
-                if (e == hipSuccess) e = launch_topk_multi_select(ts, nullptr, st);
-            }
-            if (e == hipSuccess) e = launch_topk_multi(raws[i], narrow, tp, st);
-            if (e == hipSuccess) e = launch_topk_multi_select(tp, d_keys + (size_t)row * k, st);
-            if (e != hipSuccess) break;
-            row += (uint32_t)g.size();
-        }
-        if (status == RF_OK && e == hipSuccess) e = copy_home(keys.data(), d_keys, keys.size() * sizeof(uint64_t), st);
-        else (void)hipStreamSynchronize(st);
-        if (status != RF_OK) return status;
-        if (e != hipSuccess) {
-            set_error(std::string("top-k, fused queries: ") + hipGetErrorString(e));
-            return e == hipErrorOutOfMemory ? RF_ERR_OOM : RF_ERR_HIP;
-        }
-    }
+    FusedTopk fz;
+    if (const rf_status s = topk_multi_fused(false, cs, q, corpus, op, args, k, (hipStream_t)stream, &fz); s != RF_OK) return s;
+    const std::vector<std::vector<uint32_t>>& groups = fz.groups;
+    const std::vector<char>& taken = fz.taken;
+    const std::vector<uint64_t>& keys = fz.keys;
     // decode as rf_topk_u32 does
     const bool desc = op == RF_OP_SIMILARITY;
     uint32_t row = 0;
@@ -182,6 +212,89 @@ try {
         if (taken[j]) continue;
         const rf_status s = rf_topk_u32(cs[j], corpus, op, args, k, index_base, out_score + (size_t)j * k, out_index + (size_t)j * k, out_count + j, nullptr, RF_MEM_HOST, stream);
         if (s != RF_OK) return s;
+    }
+    return RF_OK;
+}
+RF_ABI_CATCH
+
+// Row j is rf_topk_f64(cs[j], ...): the same values bit for bit in the same (score, index) order.  The grouping is rf_topk_multi_u32's with the
+// f64-valued plans; a fusable query must also keep every maximum of its scan within 65535, because the in-scan lists order by the 32-bit
+// image norm_key(dist, maximum) of the normalized distance (rf_norm_key.hpp: exact and order-preserving up to there).  Both normalized ops
+// rank by ascending key; the host turns a key back into its reduced fraction a / b and (double)a / (double)b is the double emit_fin divides
+// out of dist and maximum, so nothing of the score is lost in the 32 bits.  jaro / jaro_winkler, OSA, Damerau-Levenshtein, general weight
+// tables, queries beyond 64 symbols, tight cutoffs (early-out plans), k > 64, a maximum beyond 65535 and the odd one left over take
+// rf_topk_f64 itself.  Every fusable shape runs fused: in the same-session comparison with a loop of rf_topk_f64 (tools/bench_topk_multi_f64.py,
+// profiles/topk_multi_f64.txt: 16 queries, k = 16, 10 k .. 100 M candidates, single-length and ragged, Indel / Levenshtein / ratio) the fused road was the
+// faster one for every family and size, 2.0 x (64-bit Levenshtein, 100 M) to 15 x (10 k), and costs 0-12 % over the u32 fused kernel on the same corpus.
+rf_status rf_topk_multi_f64(const rf_comparator* const* cs, uint32_t q, const rf_corpus* corpus, rf_op op, const rf_args* args_in, uint32_t k,
+                            uint64_t index_base, double* out_score, uint64_t* out_index, uint32_t* out_count, void* stream)
+try {
+    // ---- arguments: everything here is decided before the corpus is looked at or a device is touched
+    if (!cs || !corpus || !args_in) {
+        set_error("rf_topk_multi_f64: null handle or args");
+        return RF_ERR_INVALID_ARG;
+    }
+    if (k == 0) {
+        set_error("top-k: k must be at least 1");
+        return RF_ERR_INVALID_ARG;
+    }
+    if ((int)op < 0 || (int)op > (int)RF_OP_NORMALIZED_SIMILARITY) {
+        set_error("unknown rf_op");
+        return RF_ERR_INVALID_ARG;
+    }
+    if (q == 0) return RF_OK;
+    const bool norm_op = op == RF_OP_NORMALIZED_DISTANCE || op == RF_OP_NORMALIZED_SIMILARITY;
+    for (uint32_t i = 0; i < q; ++i) {
+        if (!cs[i]) {
+            set_error("rf_topk_multi_f64: null comparator");
+            return RF_ERR_INVALID_ARG;
+        }
+        const rf_metric m = cs[i]->metric;
+        if (m == RF_JARO || m == RF_JARO_WINKLER) continue;
+        if (m == RF_FUZZ_RATIO) {
+            if (op != RF_OP_SIMILARITY && op != RF_OP_NORMALIZED_SIMILARITY) {
+                set_error("RatioBatchComparator only has similarity (fuzz.rs:115-149)");
+                return RF_ERR_INVALID_ARG;
+            }
+        } else if (!norm_op) {
+            set_error("rf_topk_multi_f64: distance and similarity of levenshtein / indel / lcs_seq / osa / damerau_levenshtein are u32-valued (rf_topk_multi_u32)");
+            return RF_ERR_INVALID_ARG;
+        }
+    }
+    // (nothing is written before every output is known to be there; only a non-empty corpus needs the row arrays)
+    if (!out_count || (corpus->n != 0 && (!out_score || !out_index))) {
+        set_error("rf_topk_multi_f64: null output");
+        return RF_ERR_INVALID_ARG;
+    }
+    for (uint32_t i = 0; i < q; ++i) out_count[i] = 0;
+    if (corpus->n == 0) return RF_OK;
+    const rf_args args_v = sanitized_args(args_in, false), *args = &args_v;
+
+    FusedTopk fz;
+    if (const rf_status s = topk_multi_fused(true, cs, q, corpus, op, args, k, (hipStream_t)stream, &fz); s != RF_OK) return s;
+    // decode: the key's fraction is the normalized distance; which value the member returns is its plan's op (a fuzz ratio: the similarity)
+    uint32_t row = 0;
+    for (const auto& g : fz.groups)
+        for (uint32_t j : g) {
+            const bool as_distance = op == RF_OP_NORMALIZED_DISTANCE && cs[j]->metric != RF_FUZZ_RATIO;
+            const uint64_t* best = fz.keys.data() + (size_t)row++ * k;
+            uint32_t m = 0;
+            for (; m < k && best[m] != ~0ull; ++m) {
+                const NormRatio r = norm_key_ratio((uint32_t)(best[m] >> 32));
+                const double nd = (double)r.a / (double)r.b;
+                out_score[(size_t)j * k + m] = as_distance ? nd : 1.0 - nd;
+                out_index[(size_t)j * k + m] = index_base + (uint32_t)best[m];
+            }
+            out_count[j] = m;
+        }
+
+    // ---- everything else: the single-query top-k, one call per query
+    for (uint32_t j = 0; j < q; ++j) {
+        if (fz.taken[j]) continue;
+        uint64_t count = 0;
+        const rf_status s = rf_topk_f64(cs[j], corpus, op, args, k, index_base, out_score + (size_t)j * k, out_index + (size_t)j * k, &count, nullptr, RF_MEM_HOST, stream);
+        if (s != RF_OK) return s;
+        out_count[j] = (uint32_t)count;
     }
     return RF_OK;
 }

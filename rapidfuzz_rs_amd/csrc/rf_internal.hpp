@@ -186,9 +186,10 @@ struct TopkMultiParams {
     ScanParams s;
     uint64_t* bound;    // [Q] lines: the query's launch-wide upper bound on its k-th best key (~0: none yet)
     uint32_t* count;    // [Q] lines: keys published to the query's segment (zero between launches)
-    uint64_t* cand;     // [Q][seg_cap] published keys: (score or ~score) << 32 | local index
+    uint64_t* cand;     // [Q][seg_cap] published keys: (score, ~score or norm_key) << 32 | local index
     uint32_t seg_cap;   // >= workgroups of the launch x topk_k
     uint32_t sample;    // topk_multi_select_kernel: 1 = leave (k-th best key + 1) in the bounds instead of writing the keys
+    uint32_t norm;      // 1 (rf_topk_multi_f64): s.op is a normalized op and the score image is norm_key(dist, maximum), rf_norm_key.hpp; topk_desc is not read
 };
 int topk_multi_grid(uint32_t tiles);  // workgroups of a launch_topk_multi over `tiles` tiles
 hipError_t launch_topk_multi(RawKind raw, bool narrow, const TopkMultiParams& tp, hipStream_t stream);

@@ -1,10 +1,11 @@
-// rf_topk_multi.hip -- top-k for Q queries in one pass over the corpus (rf_topk_multi_u32): scan_multi_kernel's tile loop with one
+// rf_topk_multi.hip -- top-k for Q queries in one pass over the corpus (rf_topk_multi_u32, rf_topk_multi_f64): scan_multi_kernel's tile loop with one
 // register-resident WaveTopK list per query instead of the dense [Q][n] result, and the selection as a launch of its own.
 // Product code: never includes or links anything from oracle/.
 #include <algorithm>
 
 #include "rf_internal.hpp"
 #include "rf_device.hpp"
+#include "rf_norm_key.hpp"
 
 namespace rf {
 
@@ -32,8 +33,12 @@ __device__ __forceinline__ void topk_multi_refresh_bound(const uint64_t* bound, 
 // No workgroup waits for another: each merges its four lists per query and appends what can still be in the answer to the query's
 // segment behind the query's counter; topk_multi_select_kernel (the next launch) selects.  A segment holds gridDim.x * k keys -- every
 // workgroup of the launch publishing a full list -- so a published key is never dropped and never overwritten.
+// kNorm (rf_topk_multi_f64): the normalized ops.  The score image is norm_key(dist, maximum) (rf_norm_key.hpp) instead of the u32 value --
+// ascending for both ops, so topk_desc is not read -- and None is emit_fin's f64 rule.  The maximum is uniform per query and tile: its
+// scale (the one f64 division) is computed once per tile and query, the candidate pays a convert, an f64 multiply and a multiply-compare;
+// nd itself -- a division per candidate -- is computed only under a cutoff, which is all that looks at it.
 // ---------------------------------------------------------------------------------------------------
-template <class State, int Q, bool kUniform>
+template <class State, int Q, bool kUniform, bool kNorm>
 __global__ __launch_bounds__(kWave* kWavesPerBlock) void topk_multi_kernel(const TopkMultiParams tp)
 {
     using Word = typename State::Word;
@@ -98,8 +103,22 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void topk_multi_kernel(const
             for (int q = 0; q < Q; ++q) {
                 const uint32_t raw = st[q].result(p.multi_len1[q], len2);
                 bool keep;
-                const uint32_t v = usize_value(p, raw, len2, &keep, p.multi_len1[q]);  // emit_usize's arithmetic; None is not offered
-                const uint64_t mine = ((uint64_t)(p.topk_desc ? ~v : v) << 32) | idx;
+                uint64_t mine;
+                if constexpr (!kNorm) {
+                    const uint32_t v = usize_value(p, raw, len2, &keep, p.multi_len1[q]);  // emit_usize's arithmetic; None is not offered
+                    mine = ((uint64_t)(p.topk_desc ? ~v : v) << 32) | idx;
+                } else {
+                    const TileFin f = tile_fin(p, p.multi_len1[q], len2);
+                    const uint32_t fmax = uniform(f.max);
+                    const double scale = norm_key_scale(fmax);
+                    const uint32_t dist = f.d0 + (uint32_t)p.fin_dR * raw;
+                    keep = true;
+                    if (p.has_cutoff) {  // emit_fin's f64 branch, to the letter
+                        const double nd = fmax == 0 ? 0.0 : (double)dist / (double)fmax;
+                        keep = p.op == RF_OP_NORMALIZED_DISTANCE ? nd <= p.cutoff_f64 : (1.0 - nd) >= p.cutoff_f64;
+                    }
+                    mine = ((uint64_t)norm_key_scaled(dist, fmax, scale) << 32) | idx;
+                }
                 if (best[q].offer(mine, valid && keep, k, lane, limit[q])) topk_multi_list_changed(tp.bound + q * kTopkMultiLine64, best[q], k, lane, limit[q]);
             }
             if ((++tiles_done & 7u) == 0) {  // every 8th tile: stream_body has the measurements
@@ -169,10 +188,15 @@ template <class State, int Q>
 static hipError_t launch_topk_multi_q(const TopkMultiParams& tp, hipStream_t stream, int grid)
 {
     const dim3 g(grid), b(kWave * kWavesPerBlock);
-    if (tp.s.tiles)
-        hipLaunchKernelGGL((topk_multi_kernel<State, Q, false>), g, b, 0, stream, tp);
+    if (tp.norm) {
+        if (tp.s.tiles)
+            hipLaunchKernelGGL((topk_multi_kernel<State, Q, false, true>), g, b, 0, stream, tp);
+        else
+            hipLaunchKernelGGL((topk_multi_kernel<State, Q, true, true>), g, b, 0, stream, tp);
+    } else if (tp.s.tiles)
+        hipLaunchKernelGGL((topk_multi_kernel<State, Q, false, false>), g, b, 0, stream, tp);
     else
-        hipLaunchKernelGGL((topk_multi_kernel<State, Q, true>), g, b, 0, stream, tp);
+        hipLaunchKernelGGL((topk_multi_kernel<State, Q, true, false>), g, b, 0, stream, tp);
     return hipGetLastError();
 }
 template <class State>
@@ -192,6 +216,7 @@ static hipError_t launch_topk_multi_state(const TopkMultiParams& tp, hipStream_t
 int topk_multi_grid(uint32_t tiles) { return std::max(1, scan_grid(tiles)); }
 
 // raw: RAW_LEV or RAW_LCS; every query single-word; `narrow` = every query <= 32 symbols.  tp.seg_cap >= grid * topk_k (checked).
+// tp.norm: a normalized op, every maximum of the launch <= kNormKeyMaxMaximum (the caller's rule: the launcher cannot see the corpus' lengths).
 hipError_t launch_topk_multi(RawKind raw, bool narrow, const TopkMultiParams& tp, hipStream_t stream)
 {
     const ScanParams& p = tp.s;

@@ -284,6 +284,18 @@ pub(crate) fn filter_multi_u32(cs: &[*const RfComparator], corpus: &crate::Corpu
         cap = most;
     }
 }
+/// The k best candidates of every comparator by a normalized score, one call (rf_topk_multi_f64): row j is (index_base + index, score) pairs ordered by
+/// (score, index) -- ascending for `RF_OP_NORMALIZED_DISTANCE`, descending for the similarity ops -- bit for bit what `normalized_*_many` returns for
+/// them.  Fusable queries share passes over the corpus, 4 (or 2) to a pass; no q x n matrix is built.
+pub(crate) fn topk_multi_f64(cs: &[*const RfComparator], corpus: &crate::Corpus, op: c_int, a: &RfArgs, k: u32, index_base: u64) -> Result<Vec<Vec<(u64, f64)>>, Error> {
+    if cs.is_empty() {
+        return Ok(Vec::new());
+    }
+    let (q, kk) = (cs.len(), k as usize);
+    let (mut score, mut idx, mut n) = (vec![0f64; q * kk], vec![0u64; q * kk], vec![0u32; q]);
+    check(unsafe { rf_topk_multi_f64(cs.as_ptr(), q as u32, corpus.0, op, a, k, index_base, score.as_mut_ptr(), idx.as_mut_ptr(), n.as_mut_ptr(), std::ptr::null_mut()) })?;
+    Ok((0..q).map(|j| (0..n[j] as usize).map(|m| (idx[j * kk + m], score[j * kk + m])).collect()).collect())
+}
 pub(crate) fn filter_f64(c: *const RfComparator, corpus: &crate::Corpus, op: c_int, a: &RfArgs, order: c_int) -> Result<Vec<(u64, f64)>, Error> {
     let mut cap = (corpus.len() / 64).max(1024) as u64;
     loop {
@@ -431,6 +443,16 @@ macro_rules! usize_metric {
                 pub fn similarity_filter_multi<C: SimilarityCutoff<usize>>(scorers: &[&Self], corpus: &Corpus, args: &Args<usize, C>, order: FilterOrder, index_base: u64) -> Result<Vec<Vec<(u64, usize)>>, Error> {
                     let hs: Vec<*const RfComparator> = scorers.iter().map(|s| s.h as *const RfComparator).collect();
                     filter_multi_u32(&hs, corpus, RF_OP_SIMILARITY, &args.lower(args.score_cutoff.cutoff()), order.lower(), index_base)
+                }
+                /// The k best candidates of every scorer by (normalized distance, index) in one call (rf_topk_multi_f64): row j belongs to `scorers[j]`.
+                pub fn normalized_distance_topk_multi<C: DistanceCutoff<f64>>(scorers: &[&Self], corpus: &Corpus, k: u32, args: &Args<f64, C>, index_base: u64) -> Result<Vec<Vec<(u64, f64)>>, Error> {
+                    let hs: Vec<*const RfComparator> = scorers.iter().map(|s| s.h as *const RfComparator).collect();
+                    topk_multi_f64(&hs, corpus, RF_OP_NORMALIZED_DISTANCE, &args.lower(args.score_cutoff.cutoff()), k, index_base)
+                }
+                /// ... and by normalized similarity, best (largest) first, ties by index.
+                pub fn normalized_similarity_topk_multi<C: SimilarityCutoff<f64>>(scorers: &[&Self], corpus: &Corpus, k: u32, args: &Args<f64, C>, index_base: u64) -> Result<Vec<Vec<(u64, f64)>>, Error> {
+                    let hs: Vec<*const RfComparator> = scorers.iter().map(|s| s.h as *const RfComparator).collect();
+                    topk_multi_f64(&hs, corpus, RF_OP_NORMALIZED_SIMILARITY, &args.lower(args.score_cutoff.cutoff()), k, index_base)
                 }
                 /// k best candidates by (distance, index); `index_base` makes shards of one logical corpus comparable.
                 pub fn topk<C: DistanceCutoff<usize>>(&self, corpus: &Corpus, k: u32, args: &Args<usize, C>, index_base: u64) -> Result<TopK, Error> {
