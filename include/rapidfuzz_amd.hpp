@@ -159,6 +159,10 @@ public:
     {
         return filter<usize_result>(c, RF_OP_SIMILARITY, a.to_c(), order);
     }
+    std::vector<std::pair<uint64_t, double>> normalized_distance_filter_many(const Corpus& c, const Args<double>& a = {}, rf_filter_order order = RF_FILTER_BY_INDEX) const
+    {
+        return filter<double>(c, RF_OP_NORMALIZED_DISTANCE, a.to_c(), order);
+    }
     std::vector<std::pair<uint64_t, double>> normalized_similarity_filter_many(const Corpus& c, const Args<double>& a = {}, rf_filter_order order = RF_FILTER_BY_INDEX) const
     {
         return filter<double>(c, RF_OP_NORMALIZED_SIMILARITY, a.to_c(), order);
@@ -228,6 +232,21 @@ public:
                                                                                           uint64_t index_base = 0)
     {
         return filter_multi(scorers, c, RF_OP_SIMILARITY, a.to_c(), order, index_base);
+    }
+
+    // ---- the same for the f64-valued scores (rf_filter_multi_f64): res[j] = normalized_*_filter_many of scorers[j] -- (index_base + index, score) pairs, in
+    // `order`, bit for bit the doubles normalized_*_many returns.  Queries under a tight cutoff (see rfgpu.h) share passes over the corpus.
+    static std::vector<std::vector<std::pair<uint64_t, double>>> normalized_distance_filter_multi(const std::vector<const BatchComparator*>& scorers, const Corpus& c,
+                                                                                                   const Args<double>& a = {}, rf_filter_order order = RF_FILTER_BY_INDEX,
+                                                                                                   uint64_t index_base = 0)
+    {
+        return filter_multi_f64(scorers, c, RF_OP_NORMALIZED_DISTANCE, a.to_c(), order, index_base);
+    }
+    static std::vector<std::vector<std::pair<uint64_t, double>>> normalized_similarity_filter_multi(const std::vector<const BatchComparator*>& scorers, const Corpus& c,
+                                                                                                     const Args<double>& a = {}, rf_filter_order order = RF_FILTER_BY_INDEX,
+                                                                                                     uint64_t index_base = 0)
+    {
+        return filter_multi_f64(scorers, c, RF_OP_NORMALIZED_SIMILARITY, a.to_c(), order, index_base);
     }
 
     // ---- the reference's per-candidate methods (a one-candidate corpus through the same kernels)
@@ -326,6 +345,26 @@ private:
             return res;
         }
     }
+    static std::vector<std::vector<std::pair<uint64_t, double>>> filter_multi_f64(const std::vector<const BatchComparator*>& scorers, const Corpus& c, rf_op op,
+                                                                                  const rf_args& a, rf_filter_order order, uint64_t index_base)
+    {
+        std::vector<const rf_comparator*> hs;
+        for (const BatchComparator* s : scorers) hs.push_back(s->h_);
+        const size_t q = hs.size();
+        if (q == 0) return {};  // (an empty vector has no data(): the C ABI refuses a null list even of no queries)
+        uint64_t cap = std::clamp<uint64_t>(c.size() / 4096, 64, 1u << 12);
+        for (;;) {  // (the device reports the true counts: at most one repeat, with room for the largest)
+            std::vector<uint64_t> index(q * cap), count(q);
+            std::vector<double> score(q * cap);
+            check(rf_filter_multi_f64(hs.data(), (uint32_t)q, c.handle(), op, &a, index_base, cap, index.data(), score.data(), count.data(), order, nullptr));
+            const uint64_t most = *std::max_element(count.begin(), count.end());
+            if (most > cap) { cap = most; continue; }
+            std::vector<std::vector<std::pair<uint64_t, double>>> res(q);
+            for (size_t j = 0; j < q; ++j)
+                for (uint64_t m = 0; m < count[j]; ++m) res[j].emplace_back(index[j * cap + m], score[j * cap + m]);
+            return res;
+        }
+    }
     template <class T>
     std::vector<std::pair<uint64_t, T>> filter(const Corpus& c, rf_op op, const rf_args& a, rf_filter_order order) const
     {
@@ -399,6 +438,20 @@ public:
         std::vector<const detail::BatchComparator<RF_FUZZ_RATIO, true>*> inner;
         for (const RatioBatchComparator* s : scorers) inner.push_back(&s->c_);
         return detail::BatchComparator<RF_FUZZ_RATIO, true>::normalized_similarity_topk_multi(inner, c, k, a, index_base);
+    }
+    /// the candidates whose ratio reaches the cutoff (rf_filter_f64): (index, ratio) pairs, in `order`
+    std::vector<std::pair<uint64_t, double>> similarity_filter_many(const Corpus& c, const detail::Args<double>& a = {}, rf_filter_order order = RF_FILTER_BY_INDEX) const
+    {
+        return c_.normalized_similarity_filter_many(c, a, order);
+    }
+    /// the same for every scorer, one call (rf_filter_multi_f64): res[j] = similarity_filter_many of scorers[j], indices offset by index_base
+    static std::vector<std::vector<std::pair<uint64_t, double>>> similarity_filter_multi(const std::vector<const RatioBatchComparator*>& scorers, const Corpus& c,
+                                                                                          const detail::Args<double>& a = {}, rf_filter_order order = RF_FILTER_BY_INDEX,
+                                                                                          uint64_t index_base = 0)
+    {
+        std::vector<const detail::BatchComparator<RF_FUZZ_RATIO, true>*> inner;
+        for (const RatioBatchComparator* s : scorers) inner.push_back(&s->c_);
+        return detail::BatchComparator<RF_FUZZ_RATIO, true>::normalized_similarity_filter_multi(inner, c, a, order, index_base);
     }
 
 private:

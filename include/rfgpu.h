@@ -70,7 +70,8 @@
  *   RF_TOPK_VIA_SCORES            1         top-k (k <= 64) as scan + one pass over the scores: 0 never, 1 multi-word Levenshtein, 2 every shape with an asm scan
  *   RF_TOPK_SAMPLE                1024      tiles of the in-scan top-k's bound sample (0: no sample pass)
  *   RF_TOPK_MULTI                 1         0: rf_topk_multi_u32 / _f64 send every query through rf_topk_u32 / _f64 instead of fusing 4 (or 2) to a pass over the corpus
- *   RF_FILTER_MULTI               1         0: rf_filter_multi_u32 sends every query through rf_filter_u32 instead of fusing tight-cutoff queries 4 (or 2) to a pass over the corpus
+ *   RF_FILTER_MULTI               1         0: rf_filter_multi_u32 / _f64 send every query through rf_filter_u32 / _f64 instead of fusing tight-cutoff queries 4 (or 2) to a pass over the corpus
+ *   RF_FILTER_MULTI_F64_ROUTE     1         0: rf_filter_multi_f64 fuses every fusable query, also the shapes its measured routing rules send through rf_filter_f64 (A/B measurements)
  *   RF_JARO_PRIV                  0         1: Jaro asm kernel gathers from a conflict-free copy of the pattern table (corpora of <= 64 symbols; measured: no gain)
  *   RF_WF_REG                     1         0: LDS rows instead of register rows for generalized weights, queries <= 64
  *   RF_TRANSLATE_DIRECT           1         0: staged translation of u32 overflow symbols
@@ -424,8 +425,8 @@ rf_status rf_topk_multi_u32(const rf_comparator *const *cs, uint32_t q, const rf
  * rf_topk_multi_u32) or a distance op of fuzz ratio is RF_ERR_INVALID_ARG -- decided before the corpus is looked at or a device is
  * touched; q == 0 is RF_OK and writes nothing; an empty corpus is RF_OK with every count 0 (outputs other than out_count may then be
  * NULL).  No error becomes an empty row.
- * Out of scope: a thresholded form (rf_filter_f64 per query), device-resident output, and a multi-GPU exchange for this call (shards
- * merge on the host, row by row). */
+ * Out of scope: device-resident output and a multi-GPU exchange for this call (shards merge on the host, row by row).  The thresholded
+ * form is rf_filter_multi_f64 below. */
 rf_status rf_topk_multi_f64(const rf_comparator *const *cs, uint32_t q, const rf_corpus *corpus, rf_op op,
                             const rf_args *args, uint32_t k, uint64_t index_base,
                             double *out_score, uint64_t *out_index, uint32_t *out_count, void *stream);
@@ -449,11 +450,40 @@ rf_status rf_topk_multi_f64(const rf_comparator *const *cs, uint32_t q, const rf
  * two above or an f64-valued metric (jaro, jaro_winkler, fuzz ratio) is RF_ERR_INVALID_ARG -- decided before the corpus is looked at or a
  * device is touched, and nothing is written; q == 0 is RF_OK and writes nothing; an empty corpus is RF_OK with every count 0.  No error
  * becomes an empty row.
- * Out of scope: f64 scores (normalized_*, the f64 metrics: rf_filter_f64 per query), device-resident output, and a multi-GPU form (shards
+ * Out of scope: f64 scores (normalized_*, the f64 metrics: rf_filter_multi_f64 below), device-resident output, and a multi-GPU form (shards
  * are separate calls with their index_base; their rows concatenate). */
 rf_status rf_filter_multi_u32(const rf_comparator *const *cs, uint32_t q, const rf_corpus *corpus, rf_op op,
                               const rf_args *args, uint64_t index_base, uint64_t capacity,
                               uint64_t *out_index, uint32_t *out_score, uint64_t *out_count,
+                              rf_filter_order order, void *stream);
+
+/* ---- the candidates within an f64 cutoff for many queries x one corpus ------------------------------
+ * Row j is exactly what rf_filter_f64(cs[j], corpus, op, args, index_base, capacity, ..., RF_MEM_HOST, order, stream) returns: the same
+ * candidates, the same doubles bit for bit, the same order, the same index_base, the same None rule under args->cutoff_f64 -- ONE cutoff
+ * for every query.  Every (comparator, op) pair rf_topk_multi_f64 accepts is accepted: RF_OP_NORMALIZED_DISTANCE /
+ * RF_OP_NORMALIZED_SIMILARITY of the usize metrics, fuzz ratio with its similarity ops (with and without
+ * RF_FLAG_RATIO_INDEL_NORMALIZATION), every op of jaro / jaro_winkler.  Outputs are HOST arrays as in rf_filter_multi_u32, out_score
+ * holding doubles: out_index and out_score row-major [q][capacity], out_count[q]; out_count[j] is ALWAYS the true number of matches, and
+ * when it exceeds `capacity` row j holds `capacity` valid, distinct qualifying pairs in the requested order among themselves;
+ * capacity == 0 is a pure count (the two row arrays may then be NULL).  order: RF_FILTER_BY_INDEX, RF_FILTER_BY_SCORE (best first --
+ * ascending for normalized_distance, descending for the similarity ops -- ties by ascending index) or RF_FILTER_ANY.
+ * Fused 4 (or 2) to a pass over the corpus, where rf_filter_multi_u32's rule and rf_topk_multi_f64's both hold: levenshtein (uniform or
+ * Indel-like weights) / indel / lcs_seq / fuzz ratio queries of <= 64 symbols under a TIGHT cutoff (the planner's early-out rule on the
+ * f64 cutoff) whose largest possible maximum over this corpus is <= 65535.  The pass keeps or drops a candidate by the very f64 compare
+ * of the single-query call and stores the exact 32-bit image of dist / maximum (floor(dist * 2^32 / maximum)), which the host turns back
+ * into the double rf_filter_f64 returns.  Every other query (jaro, jaro_winkler, osa, damerau_levenshtein, general weight tables, longer
+ * queries, no cutoff (NaN) or a loose one, a u32 query with overflow-class symbols, a maximum beyond 65535, the odd one left over, and
+ * levenshtein under a cutoff tight enough for a first look at column 8 over a single-length corpus of 3 x 2^23 candidates or more, where
+ * the per-query head-plane scan measured faster than the fused pass) goes through rf_filter_f64 itself, one call per query.  RF_TRACE_PLAN names the groups; RF_FILTER_MULTI=0 sends every query per query.
+ * Errors: a null cs / corpus / args / out_count / comparator, a null row array with capacity != 0, an unknown order, an unknown op,
+ * RF_OP_DISTANCE / RF_OP_SIMILARITY of a usize metric (u32-valued: rf_filter_multi_u32) or a distance op of fuzz ratio is
+ * RF_ERR_INVALID_ARG -- decided before the corpus is looked at or a device is touched, and nothing is written; q == 0 is RF_OK and
+ * writes nothing; an empty corpus is RF_OK with every count 0.  No error becomes an empty row.
+ * Out of scope: a wider key for maxima beyond 65535, device-resident output, and a multi-GPU form (shards are separate calls with their
+ * index_base; their rows concatenate). */
+rf_status rf_filter_multi_f64(const rf_comparator *const *cs, uint32_t q, const rf_corpus *corpus, rf_op op,
+                              const rf_args *args, uint64_t index_base, uint64_t capacity,
+                              uint64_t *out_index, double *out_score, uint64_t *out_count,
                               rf_filter_order order, void *stream);
 
 /* ---- top-k ------------------------------------------------------------------------------------

@@ -242,13 +242,16 @@ class BatchComparator:
     @classmethod
     def filter_multi(cls, comparators: Sequence["BatchComparator"], op: int, corpus: Corpus, args: Optional[Args] = None, capacity: Optional[int] = None,
                      order: int = N.FILTER_BY_INDEX, index_base: int = 0, stream=None, *, score_cutoff=None, score_hint=None, weights=None, prefix_weight=None):
-        """[(indices uint64[m_j], scores uint32[m_j]) for every comparator]: pair j is `comparators[j].filter_many(op, corpus, ...)` (rf_filter_multi_u32) --
-        distance or similarity of the usize metrics, one cutoff for every query.  Queries of <= 64 symbols of one metric under a tight cutoff are fused 4 at a
-        time into one pass over the corpus that appends the matches to a compact list per query; no [q, n] matrix is built.  `capacity` bounds every
-        row; None = a default, then one repeat with room for the largest count if a row overflowed.  `last_filter_counts` (on the class the call was made
-        through) holds the true counts."""
+        """[(indices uint64[m_j], scores[m_j]) for every comparator]: pair j is `comparators[j].filter_many(op, corpus, ...)` -- uint32 scores for distance or
+        similarity of the usize metrics (rf_filter_multi_u32), float64 scores for normalized_* and for the float classes (jaro, jaro_winkler, ratio),
+        rf_filter_multi_f64; one cutoff for every query.  Queries of <= 64 symbols of one metric under a tight cutoff are fused 4 at a time into one pass
+        over the corpus that appends the matches to a compact list per query; no [q, n] matrix is built.  `capacity` bounds every row; None = a default,
+        then one repeat with room for the largest count if a row overflowed.  `last_filter_counts` (on the class the call was made through) holds the
+        true counts."""
         a = _mk_args(args, score_cutoff, score_hint, weights, prefix_weight)
-        ca = a.to_c(False)
+        is_f = cls.FLOAT or op >= N.OP_NORMALIZED_DISTANCE
+        ca = a.to_c(is_f)
+        fn = N.lib().rf_filter_multi_f64 if is_f else N.lib().rf_filter_multi_u32
         q = len(comparators)
         if q == 0:
             return []
@@ -257,10 +260,9 @@ class BatchComparator:
         cap = int(capacity) if capacity is not None else max(64, min(len(corpus) // 4096, 1 << 12))
         while True:
             idx = np.empty((q, max(cap, 1)), dtype=np.uint64)
-            sc = np.empty((q, max(cap, 1)), dtype=np.uint32)
+            sc = np.empty((q, max(cap, 1)), dtype=np.float64 if is_f else np.uint32)
             cnt = np.zeros(q, dtype=np.uint64)
-            N.check(N.lib().rf_filter_multi_u32(hs, q, corpus._h, op, C.byref(ca), index_base, cap, idx.ctypes.data if cap else None, sc.ctypes.data if cap else None,
-                                                cnt.ctypes.data, order, stream))
+            N.check(fn(hs, q, corpus._h, op, C.byref(ca), index_base, cap, idx.ctypes.data if cap else None, sc.ctypes.data if cap else None, cnt.ctypes.data, order, stream))
             if capacity is not None or int(cnt.max()) <= cap:
                 cls.last_filter_counts = [int(x) for x in cnt]
                 return [(idx[j, : min(int(cnt[j]), cap)].copy(), sc[j, : min(int(cnt[j]), cap)].copy()) for j in range(q)]

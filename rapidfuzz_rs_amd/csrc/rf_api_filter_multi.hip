@@ -1,17 +1,185 @@
-// rf_api_filter_multi.hip -- rf_filter_multi_u32: the (index, score) pairs within the cutoff of each of q queries, fusable queries 4 (then 2) to a
-// pass over the corpus (rf_filter_multi.hip), every other query through rf_filter_u32 (rf_host.hpp has the shared declarations).
+// rf_api_filter_multi.hip -- rf_filter_multi_u32 / rf_filter_multi_f64: the (index, score) pairs within the cutoff of each of q queries, fusable queries 4
+// (then 2) to a pass over the corpus (rf_filter_multi.hip), every other query through rf_filter_u32 / rf_filter_f64 (rf_host.hpp has the shared declarations).
 // Product code: never includes or links anything from oracle/.
 #include <algorithm>
 
 #include "rf_host.hpp"
 
+#include "rf_filter_multi_rows.hpp"
+
 extern "C" {
 
 constexpr size_t kHeadPlaneWins = size_t(1) << 25;  // candidates of a single-length corpus from which small-cutoff Levenshtein queries go per query (see the planner below)
+constexpr size_t kHeadPlaneWinsF64 = size_t(3) << 23;  // the same for the f64 plans of rf_filter_multi_f64 (25.2 M: see the planner below)
 // A/B switch: 0 sends every query down the per-query road (identical results)
 static bool sw_filter_multi() { static const bool v = env_on("RF_FILTER_MULTI"); return v; }
+// A/B switch of the f64 planner: 0 fuses every fusable query of rf_filter_multi_f64, also the shapes its measured routing rules send per query
+static bool sw_filter_multi_f64_route() { static const bool v = env_on("RF_FILTER_MULTI_F64_ROUTE"); return v; }
 
-// Row j is rf_filter_u32(cs[j], ..., RF_MEM_HOST, order, ...).  Queries are planned as rf_topk_multi_u32 plans them and grouped under its rules, with ONE
+// What rf_filter_multi_u32 and rf_filter_multi_f64 share, after their argument checks: plan every query, group the fusable ones, run the groups and bring
+// their counters and key rows home.  `norm` (rf_filter_multi_f64): f64-valued plans, the normalized kernels, and one more condition on a fusable query -- the
+// largest maximum it can meet in this corpus fits the 32-bit score image (rf_topk_multi_f64's rule).
+struct FusedFilter {
+    std::vector<std::vector<uint32_t>> groups;  // members of each fused group, as indices into cs
+    std::vector<char> taken;                    // [q] 1: the query is in a group
+    uint32_t seg_cap = 0;                       // keys a row can hold: min(capacity, n)
+    // the results at home.  Row r = the r-th fused member in group order: count(r) is its true number of matches, keys(r) its first min(count, seg_cap) keys in
+    // the order of arrival -- (score, ~score or norm_key) << 32 | local index
+    std::vector<uint8_t> home;
+    std::vector<uint64_t> big;  // (the two-step road: [fused][width], width = the longest list held)
+    size_t ctl_bytes = 0, width = 0;
+    bool one_copy = true;
+    uint32_t count(uint32_t r) const { return reinterpret_cast<const uint32_t*>(home.data())[(size_t)r * kFilterMultiLine32]; }
+    uint64_t* keys(uint32_t r) { return one_copy ? reinterpret_cast<uint64_t*>(home.data() + ctl_bytes) + (size_t)r * seg_cap : big.data() + (size_t)r * width; }
+};
+static rf_status filter_multi_fused(bool norm, const rf_comparator* const* cs, uint32_t q, const rf_corpus* corpus, rf_op op, const rf_args* args, uint64_t capacity,
+                                    hipStream_t st, FusedFilter* out)
+{
+    // ---- plan every query; which ones can be fused
+    std::vector<ScanParams> ps(q);
+    std::vector<RawKind> raws(q, RAW_LEV);
+    std::vector<const rf_comparator*> eff(q, nullptr);
+    std::vector<ComparatorRef> holds(q);
+    std::vector<char> fusable(q, 0);
+    if (sw_filter_multi())
+        for (uint32_t i = 0; i < q; ++i) {
+            // (a query that does not resolve -- overflow-class symbols need a translated image of the corpus -- or does not plan goes to
+            // the single-query call, which serves it or reports why not)
+            if (resolve(cs[i], corpus, &eff[i], &holds[i]) != RF_OK) continue;
+            if (plan(eff[i], corpus, op, args, norm, &ps[i], &raws[i]) != RF_OK) continue;
+            fusable[i] = (raws[i] == RAW_LEV || raws[i] == RAW_LCS) && eff[i]->words == 1 && !ps[i].long_words_pad && ps[i].early;
+            if (norm && fusable[i]) {
+                // the 32-bit score image (rf_norm_key.hpp) is exact while every maximum of the scan is <= 65535; the maximum grows with the candidate's length
+                const uint64_t len1 = ps[i].len1, len2 = corpus->max_len;
+                const uint64_t largest = (uint64_t)ps[i].fin_mS * (len1 + len2) + (uint64_t)ps[i].fin_mM * std::max(len1, len2);
+                fusable[i] = largest <= kNormKeyMaxMaximum;
+            }
+            // The one shape the fused road lost (tools/bench_filter_multi.py, profiles/filter_multi.txt): Levenshtein under a small cutoff over a LARGE single-length
+            // corpus, where rf_filter_u32 takes its first look from the 8-byte head plane and compacts lanes (6-8 B per pair, 8 columns) while a fused group reads
+            // the payload's 16-byte first chunk: 100 M x 64, cutoff 3, 16 / 256 queries 5.67 / 89.5 ms fused against 3.00 / 53.7 ms per query; at 10 M the fused
+            // road still wins (0.92 / 14.1 against 1.64 / 23.9 ms).  Between the two sizes the boundary is interpolated from those four times (fixed cost + slope of
+            // either road: about 2^25 candidates for a group of four); the one size measured beside it, 30 M, is level at 16 queries and 1.10 x at 256
+            // (profiles/filter_multi_copy.txt).  A query whose length window is empty stays fused: it launches nothing.
+            // The f64 plans (tools/bench_filter_multi_f64.py, profiles/filter_multi_f64.txt; 16 / 256 queries of 64 symbols): rf_filter_f64 takes the same head-plane road
+            // for such a query -- first_check <= 8 is normalized_similarity >= 0.95 over 64-symbol candidates, and RF_TRACE_PLAN shows heads8=1 for its scans -- and the
+            // fused road, which also pays an f64 division per look, falls behind EARLIER.  normalized_similarity >= 0.95, fused (RF_FILTER_MULTI_F64_ROUTE=0) against the loop: 20 M
+            // 1.39 / 20.4 ms against 1.93 / 27.0 (1.39 / 1.33 x), 24 M 1.65 / 24.2 against 1.72 / 30.6 (1.04 / 1.27 x; second run 1.12 / 1.13 x), 30 M 2.02 / 30.0 against
+            // 1.98 / 32.5 (0.98 / 1.08 x; first session 0.96 / 1.03 x: at 16 queries the fused road LOSES), 100 M 6.24 / 96.9 against 3.02 / 49.7 (0.48 / 0.51 x).  So the
+            // boundary sits between the last size where both query counts win by more than the spread, 24 M, and the first where one loses, 30 M: 3 x 2^23 = 25.2 M.
+            // A cutoff whose first look comes later (normalized_similarity >= 0.9: first_check 10, no head plane per query) stays fused at every size: 100 M 8.58 / 135.9 ms
+            // against 11.01 / 172.2 (1.28 / 1.27 x).
+            const size_t head_plane_wins = norm ? kHeadPlaneWinsF64 : kHeadPlaneWins;
+            if (fusable[i] && raws[i] == RAW_LEV && corpus->uniform && corpus->n >= head_plane_wins && ps[i].first_check <= 8 && ps[i].tile_begin < ps[i].tile_end &&
+                (!norm || sw_filter_multi_f64_route()))
+                fusable[i] = 0;
+        }
+    // (ps[].op: what the kernel computes -- a fuzz ratio plans to RF_OP_NORMALIZED_SIMILARITY whichever similarity op was asked for)
+    auto same_group = [&](uint32_t a, uint32_t b) {
+        return raws[a] == raws[b] && ps[a].finish == ps[b].finish && ps[a].factor == ps[b].factor && ps[a].op == ps[b].op &&
+               (ps[a].len1 <= 32) == (ps[b].len1 <= 32);
+    };
+    // (rows are independent, so a group's members need not be neighbours)
+    std::vector<std::vector<uint32_t>>& groups = out->groups;
+    std::vector<char>& taken = out->taken;
+    taken.assign(q, 0);
+    for (uint32_t i = 0; i < q; ++i) {
+        if (taken[i] || !fusable[i]) continue;
+        std::vector<uint32_t> g{i};
+        for (uint32_t j = i + 1; j < q && g.size() < (size_t)kMaxMulti; ++j)
+            if (!taken[j] && fusable[j] && same_group(i, j)) g.push_back(j);
+        if (g.size() == 3) g.pop_back();
+        if (g.size() < 2) continue;  // the odd one left over
+        for (uint32_t m : g) taken[m] = 1;
+        groups.push_back(std::move(g));
+    }
+    uint32_t fused = 0;
+    for (const auto& g : groups) fused += (uint32_t)g.size();
+    if (sw_trace_plan()) {
+        std::string sizes;
+        for (const auto& g : groups) sizes += (sizes.empty() ? "" : ",") + std::to_string(g.size());
+        std::fprintf(stderr, "[rf plan] %s: q=%u fused_groups=[%s] per_query=%u\n", norm ? "filter_multi_f64" : "filter_multi", q, sizes.c_str(), q - fused);
+    }
+
+    // ---- the fused groups: everything enqueued, then the results home
+    const uint32_t seg_cap = out->seg_cap = (uint32_t)std::min<uint64_t>(capacity, corpus->n);
+    if (fused) {
+        DeviceGuard guard(corpus->device);
+        if (!guard.ok) {
+            set_error("cannot select the corpus' device");
+            return RF_ERR_NO_DEVICE;
+        }
+        ScratchSet sc(st);
+        // one block: [fused counter lines | fused segments of seg_cap keys], row r = the r-th fused member in group order
+        constexpr size_t kLine = kFilterMultiLine32 * sizeof(uint32_t);
+        constexpr size_t kOneCopyBytes = 256u << 10;
+        const size_t ctl_bytes = out->ctl_bytes = (size_t)fused * kLine, seg_bytes = (size_t)fused * seg_cap * sizeof(uint64_t);
+        uint8_t* block = nullptr;
+        RF_HIP(sc.get(&block, ctl_bytes + seg_bytes));
+        uint32_t* d_count = reinterpret_cast<uint32_t*>(block);
+        uint64_t* d_cand = reinterpret_cast<uint64_t*>(block + ctl_bytes);
+        hipError_t e = hipMemsetAsync(d_count, 0, ctl_bytes, st);
+        rf_status status = RF_OK;
+        uint32_t row = 0;
+        for (const auto& g : groups) {
+            if (e != hipSuccess) break;
+            const uint32_t i = g[0];
+            FilterMultiParams fp{};
+            fp.s = ps[i];
+            ScanParams& p = fp.s;
+            p.out = nullptr, p.prefill_none = 0, p.tile_step = 1;
+            p.multi_q = (uint32_t)g.size();
+            p.topk_desc = op == RF_OP_SIMILARITY;  // (not read under norm: both normalized ops store the ascending norm_key)
+            fp.norm = norm ? 1u : 0u;
+            // the union of the members' length windows (plan(): a member's tiles outside its own are None by their length alone; an empty window: tile_begin == tile_end)
+            uint32_t t0 = corpus->n_tiles, t1 = 0;
+            for (size_t m = 0; m < g.size() && status == RF_OK; ++m) {
+                const ScanParams& pm = ps[g[m]];
+                p.multi_len1[m] = pm.len1;
+                if (pm.tile_begin < pm.tile_end) t0 = std::min(t0, pm.tile_begin), t1 = std::max(t1, std::min(pm.tile_end, corpus->n_tiles));
+                status = comparator_device_pm(eff[g[m]], corpus->device, &p.multi_pm[m]);
+            }
+            if (status != RF_OK) break;
+            p.tile_begin = t0, p.tile_end = std::max(t0, t1);
+            fp.count = d_count + (size_t)row * kFilterMultiLine32;
+            fp.cand = seg_cap ? d_cand + (size_t)row * seg_cap : nullptr;
+            fp.seg_cap = seg_cap;
+            e = launch_filter_multi(raws[i], p.len1 <= 32, fp, st);
+            row += (uint32_t)g.size();
+        }
+        std::vector<uint8_t>& home = out->home;
+        std::vector<uint64_t>& big = out->big;
+        size_t& width = out->width = seg_cap;
+        const bool one_copy = out->one_copy = seg_bytes <= kOneCopyBytes;
+        if (status == RF_OK && e == hipSuccess) {
+            home.resize(one_copy ? ctl_bytes + seg_bytes : ctl_bytes);
+            e = copy_home(home.data(), block, home.size(), st);
+            if (e == hipSuccess && !one_copy) {
+                // the counters say how much of the segments is filled: the first `width` keys of EVERY segment in one strided copy, whatever the number of rows
+                width = 0;
+                for (uint32_t r = 0; r < fused; ++r)
+                    width = std::max<size_t>(width, std::min(reinterpret_cast<const uint32_t*>(home.data())[(size_t)r * kFilterMultiLine32], seg_cap));
+                if (width) {
+                    big.resize((size_t)fused * width);
+                    e = hipMemcpy2DAsync(big.data(), width * sizeof(uint64_t), d_cand, (size_t)seg_cap * sizeof(uint64_t), width * sizeof(uint64_t), fused,
+                                         hipMemcpyDeviceToHost, st);
+                    const hipError_t es = hipStreamSynchronize(st);
+                    if (e == hipSuccess) e = es;
+                }
+            }
+        } else {
+            (void)hipStreamSynchronize(st);
+        }
+        if (status != RF_OK) return status;
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            set_error(std::string("filter, fused queries: ") + hipGetErrorString(e));
+            return e == hipErrorOutOfMemory ? RF_ERR_OOM : RF_ERR_HIP;
+        }
+    }
+    return RF_OK;
+}
+
+// Row j is rf_filter_u32(cs[j], ..., RF_MEM_HOST, order, ...).  Queries are planned as rf_topk_multi_u32 plans them and grouped under its rules (filter_multi_fused), with ONE
 // difference: here a query is fused when plan() set `early` -- the cutoff is tight -- and goes per query when it did not.  Under a tight cutoff nearly every
 // tile dies for all members at the first look, the rare passer costs one atomic per tile and member, and the compact lists need no n-entry vector; without one
 // (or under a loose one) every candidate would be appended and rf_filter_u32's scan + compaction is the better road.  OSA, Damerau-Levenshtein, general weight
@@ -55,138 +223,17 @@ try {
     if (corpus->n == 0) return RF_OK;
     const rf_args args_v = sanitized_args(args_in, false), *args = &args_v;
 
-    // ---- plan every query; which ones can be fused
-    std::vector<ScanParams> ps(q);
-    std::vector<RawKind> raws(q, RAW_LEV);
-    std::vector<const rf_comparator*> eff(q, nullptr);
-    std::vector<ComparatorRef> holds(q);
-    std::vector<char> fusable(q, 0);
-    if (sw_filter_multi())
-        for (uint32_t i = 0; i < q; ++i) {
-            // (a query that does not resolve -- overflow-class symbols need a translated image of the corpus -- or does not plan goes to
-            // rf_filter_u32, which serves it or reports why not)
-            if (resolve(cs[i], corpus, &eff[i], &holds[i]) != RF_OK) continue;
-            if (plan(eff[i], corpus, op, args, false, &ps[i], &raws[i]) != RF_OK) continue;
-            fusable[i] = (raws[i] == RAW_LEV || raws[i] == RAW_LCS) && eff[i]->words == 1 && !ps[i].long_words_pad && ps[i].early;
-            // The one shape the fused road lost (tools/bench_filter_multi.py, profiles/filter_multi.txt): Levenshtein under a small cutoff over a LARGE single-length
-            // corpus, where rf_filter_u32 takes its first look from the 8-byte head plane and compacts lanes (6-8 B per pair, 8 columns) while a fused group reads
-            // the payload's 16-byte first chunk: 100 M x 64, cutoff 3, 16 / 256 queries 5.67 / 89.5 ms fused against 3.00 / 53.7 ms per query; at 10 M the fused
-            // road still wins (0.92 / 14.1 against 1.64 / 23.9 ms).  Between the two sizes the boundary is interpolated from those four times (fixed cost + slope of
-            // either road: about 2^25 candidates for a group of four); the one size measured beside it, 30 M, is level at 16 queries and 1.10 x at 256
-            // (profiles/filter_multi_copy.txt).  A query whose length window is empty stays fused: it launches nothing.
-            if (fusable[i] && raws[i] == RAW_LEV && corpus->uniform && corpus->n >= kHeadPlaneWins && ps[i].first_check <= 8 && ps[i].tile_begin < ps[i].tile_end)
-                fusable[i] = 0;
-        }
-    auto same_group = [&](uint32_t a, uint32_t b) {
-        return raws[a] == raws[b] && ps[a].finish == ps[b].finish && ps[a].factor == ps[b].factor && ps[a].op == ps[b].op &&
-               (ps[a].len1 <= 32) == (ps[b].len1 <= 32);
-    };
-    // (rows are independent, so a group's members need not be neighbours)
-    std::vector<std::vector<uint32_t>> groups;
-    std::vector<char> taken(q, 0);
-    for (uint32_t i = 0; i < q; ++i) {
-        if (taken[i] || !fusable[i]) continue;
-        std::vector<uint32_t> g{i};
-        for (uint32_t j = i + 1; j < q && g.size() < (size_t)kMaxMulti; ++j)
-            if (!taken[j] && fusable[j] && same_group(i, j)) g.push_back(j);
-        if (g.size() == 3) g.pop_back();
-        if (g.size() < 2) continue;  // the odd one left over
-        for (uint32_t m : g) taken[m] = 1;
-        groups.push_back(std::move(g));
-    }
-    uint32_t fused = 0;
-    for (const auto& g : groups) fused += (uint32_t)g.size();
-    if (sw_trace_plan()) {
-        std::string sizes;
-        for (const auto& g : groups) sizes += (sizes.empty() ? "" : ",") + std::to_string(g.size());
-        std::fprintf(stderr, "[rf plan] filter_multi: q=%u fused_groups=[%s] per_query=%u\n", q, sizes.c_str(), q - fused);
-    }
-
-    // ---- the fused groups: everything enqueued, then the results home
-    hipStream_t st = (hipStream_t)stream;
-    const bool desc = op == RF_OP_SIMILARITY;
-    const uint32_t seg_cap = (uint32_t)std::min<uint64_t>(capacity, corpus->n);
-    if (fused) {
-        DeviceGuard guard(corpus->device);
-        if (!guard.ok) {
-            set_error("cannot select the corpus' device");
-            return RF_ERR_NO_DEVICE;
-        }
-        ScratchSet sc(st);
-        // one block: [fused counter lines | fused segments of seg_cap keys], row r = the r-th fused member in group order
-        constexpr size_t kLine = kFilterMultiLine32 * sizeof(uint32_t);
-        constexpr size_t kOneCopyBytes = 256u << 10;
-        const size_t ctl_bytes = (size_t)fused * kLine, seg_bytes = (size_t)fused * seg_cap * sizeof(uint64_t);
-        uint8_t* block = nullptr;
-        RF_HIP(sc.get(&block, ctl_bytes + seg_bytes));
-        uint32_t* d_count = reinterpret_cast<uint32_t*>(block);
-        uint64_t* d_cand = reinterpret_cast<uint64_t*>(block + ctl_bytes);
-        hipError_t e = hipMemsetAsync(d_count, 0, ctl_bytes, st);
-        rf_status status = RF_OK;
+    FusedFilter fz;
+    if (const rf_status s = filter_multi_fused(false, cs, q, corpus, op, args, capacity, (hipStream_t)stream, &fz); s != RF_OK) return s;
+    // order and decode as rf_filter_u32 does: by index ascending, or best score first with ties by index (a plain sort of the keys)
+    {
+        const bool desc = op == RF_OP_SIMILARITY;
         uint32_t row = 0;
-        for (const auto& g : groups) {
-            if (e != hipSuccess) break;
-            const uint32_t i = g[0];
-            FilterMultiParams fp{};
-            fp.s = ps[i];
-            ScanParams& p = fp.s;
-            p.out = nullptr, p.prefill_none = 0, p.tile_step = 1;
-            p.multi_q = (uint32_t)g.size();
-            p.topk_desc = desc;
-            // the union of the members' length windows (plan(): a member's tiles outside its own are None by their length alone; an empty window: tile_begin == tile_end)
-            uint32_t t0 = corpus->n_tiles, t1 = 0;
-            for (size_t m = 0; m < g.size() && status == RF_OK; ++m) {
-                const ScanParams& pm = ps[g[m]];
-                p.multi_len1[m] = pm.len1;
-                if (pm.tile_begin < pm.tile_end) t0 = std::min(t0, pm.tile_begin), t1 = std::max(t1, std::min(pm.tile_end, corpus->n_tiles));
-                status = comparator_device_pm(eff[g[m]], corpus->device, &p.multi_pm[m]);
-            }
-            if (status != RF_OK) break;
-            p.tile_begin = t0, p.tile_end = std::max(t0, t1);
-            fp.count = d_count + (size_t)row * kFilterMultiLine32;
-            fp.cand = seg_cap ? d_cand + (size_t)row * seg_cap : nullptr;
-            fp.seg_cap = seg_cap;
-            e = launch_filter_multi(raws[i], p.len1 <= 32, fp, st);
-            row += (uint32_t)g.size();
-        }
-        std::vector<uint8_t> home;
-        std::vector<uint64_t> big;  // (the two-step road: [fused][width], width = the longest list held)
-        size_t width = seg_cap;
-        const bool one_copy = seg_bytes <= kOneCopyBytes;
-        if (status == RF_OK && e == hipSuccess) {
-            home.resize(one_copy ? ctl_bytes + seg_bytes : ctl_bytes);
-            e = copy_home(home.data(), block, home.size(), st);
-            if (e == hipSuccess && !one_copy) {
-                // the counters say how much of the segments is filled: the first `width` keys of EVERY segment in one strided copy, whatever the number of rows
-                width = 0;
-                for (uint32_t r = 0; r < fused; ++r)
-                    width = std::max<size_t>(width, std::min(reinterpret_cast<const uint32_t*>(home.data())[(size_t)r * kFilterMultiLine32], seg_cap));
-                if (width) {
-                    big.resize((size_t)fused * width);
-                    e = hipMemcpy2DAsync(big.data(), width * sizeof(uint64_t), d_cand, (size_t)seg_cap * sizeof(uint64_t), width * sizeof(uint64_t), fused,
-                                         hipMemcpyDeviceToHost, st);
-                    const hipError_t es = hipStreamSynchronize(st);
-                    if (e == hipSuccess) e = es;
-                }
-            }
-        } else {
-            (void)hipStreamSynchronize(st);
-        }
-        if (status != RF_OK) return status;
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            for (uint32_t i = 0; i < q; ++i) out_count[i] = 0;
-            set_error(std::string("filter, fused queries: ") + hipGetErrorString(e));
-            return e == hipErrorOutOfMemory ? RF_ERR_OOM : RF_ERR_HIP;
-        }
-        // order and decode as rf_filter_u32 does: by index ascending, or best score first with ties by index (a plain sort of the keys)
-        const uint32_t* counts = reinterpret_cast<const uint32_t*>(home.data());
-        row = 0;
-        for (const auto& g : groups)
+        for (const auto& g : fz.groups)
             for (uint32_t j : g) {
                 const uint32_t r = row++;
-                const uint32_t count = counts[(size_t)r * kFilterMultiLine32], have = std::min(count, seg_cap);
-                uint64_t* keys = one_copy ? reinterpret_cast<uint64_t*>(home.data() + ctl_bytes) + (size_t)r * seg_cap : big.data() + (size_t)r * width;
+                const uint32_t count = fz.count(r), have = std::min(count, fz.seg_cap);
+                uint64_t* keys = fz.keys(r);
                 if (order == RF_FILTER_BY_SCORE)
                     std::sort(keys, keys + have);
                 else if (order == RF_FILTER_BY_INDEX)
@@ -202,8 +249,82 @@ try {
 
     // ---- everything else: the single-query filter, one call per query
     for (uint32_t j = 0; j < q; ++j) {
-        if (taken[j]) continue;
+        if (fz.taken[j]) continue;
         const rf_status s = rf_filter_u32(cs[j], corpus, op, args, index_base, capacity, capacity ? out_index + (size_t)j * capacity : nullptr,
+                                          capacity ? out_score + (size_t)j * capacity : nullptr, out_count + j, RF_MEM_HOST, order, stream);
+        if (s != RF_OK) return s;
+    }
+    return RF_OK;
+}
+RF_ABI_CATCH
+
+// Row j is rf_filter_f64(cs[j], ..., RF_MEM_HOST, order, ...): the same pairs, the same doubles bit for bit, in the same order.  The grouping is
+// rf_filter_multi_u32's with the f64-valued plans -- plan() sets `early` from the f64 cutoff: a normalized distance below 0.7 (Levenshtein) / 0.4 (LCS family) still
+// allowed -- and, as in rf_topk_multi_f64, a fusable query must keep every maximum of its scan within 65535: the kernel keeps or drops a candidate by emit_fin's
+// own f64 compare and stores norm_key(dist, maximum) (rf_norm_key.hpp), which the host orders and turns back into the double (rf_filter_multi_rows.hpp).  jaro /
+// jaro_winkler, OSA, Damerau-Levenshtein, general weight tables, queries beyond 64 symbols, no cutoff (NaN) or a loose one, a maximum beyond 65535 and the odd one
+// left over take rf_filter_f64 itself.
+rf_status rf_filter_multi_f64(const rf_comparator* const* cs, uint32_t q, const rf_corpus* corpus, rf_op op, const rf_args* args_in, uint64_t index_base,
+                              uint64_t capacity, uint64_t* out_index, double* out_score, uint64_t* out_count, rf_filter_order order, void* stream)
+try {
+    // ---- arguments: everything here is decided before the corpus is looked at or a device is touched, and before anything is written
+    if (!cs || !corpus || !args_in || !out_count) {
+        set_error("rf_filter_multi_f64: null handle, args or count");
+        return RF_ERR_INVALID_ARG;
+    }
+    if (capacity && (!out_index || !out_score)) {
+        set_error("rf_filter_multi_f64: null output with a non-zero capacity");
+        return RF_ERR_INVALID_ARG;
+    }
+    if ((int)order < 0 || (int)order > (int)RF_FILTER_ANY) {
+        set_error("rf_filter_multi_f64: unknown order");
+        return RF_ERR_INVALID_ARG;
+    }
+    if ((int)op < 0 || (int)op > (int)RF_OP_NORMALIZED_SIMILARITY) {
+        set_error("unknown rf_op");
+        return RF_ERR_INVALID_ARG;
+    }
+    const bool norm_op = op == RF_OP_NORMALIZED_DISTANCE || op == RF_OP_NORMALIZED_SIMILARITY;
+    // (a null or unacceptable comparator anywhere in the list is an error whatever q's other members are; q == 0 has none)
+    for (uint32_t i = 0; i < q; ++i) {
+        if (!cs[i]) {
+            set_error("rf_filter_multi_f64: null comparator");
+            return RF_ERR_INVALID_ARG;
+        }
+        const rf_metric m = cs[i]->metric;
+        if (m == RF_JARO || m == RF_JARO_WINKLER) continue;
+        if (m == RF_FUZZ_RATIO) {
+            if (op != RF_OP_SIMILARITY && op != RF_OP_NORMALIZED_SIMILARITY) {
+                set_error("RatioBatchComparator only has similarity (fuzz.rs:115-149)");
+                return RF_ERR_INVALID_ARG;
+            }
+        } else if (!norm_op) {
+            set_error("rf_filter_multi_f64: distance and similarity of levenshtein / indel / lcs_seq / osa / damerau_levenshtein are u32-valued (rf_filter_multi_u32)");
+            return RF_ERR_INVALID_ARG;
+        }
+    }
+    if (q == 0) return RF_OK;
+    for (uint32_t i = 0; i < q; ++i) out_count[i] = 0;
+    if (corpus->n == 0) return RF_OK;
+    const rf_args args_v = sanitized_args(args_in, false), *args = &args_v;
+
+    FusedFilter fz;
+    if (const rf_status s = filter_multi_fused(true, cs, q, corpus, op, args, capacity, (hipStream_t)stream, &fz); s != RF_OK) return s;
+    // order and decode (rf_filter_multi_rows.hpp); which value a member returns is its plan's op (a fuzz ratio: the similarity)
+    uint32_t row = 0;
+    for (const auto& g : fz.groups)
+        for (uint32_t j : g) {
+            const uint32_t r = row++;
+            const uint32_t count = fz.count(r), have = std::min(count, fz.seg_cap);
+            const bool as_distance = op == RF_OP_NORMALIZED_DISTANCE && cs[j]->metric != RF_FUZZ_RATIO;
+            if (have) filter_multi_f64_row(fz.keys(r), have, order, as_distance, index_base, out_index + (size_t)j * capacity, out_score + (size_t)j * capacity);
+            out_count[j] = count;
+        }
+
+    // ---- everything else: the single-query filter, one call per query
+    for (uint32_t j = 0; j < q; ++j) {
+        if (fz.taken[j]) continue;
+        const rf_status s = rf_filter_f64(cs[j], corpus, op, args, index_base, capacity, capacity ? out_index + (size_t)j * capacity : nullptr,
                                           capacity ? out_score + (size_t)j * capacity : nullptr, out_count + j, RF_MEM_HOST, order, stream);
         if (s != RF_OK) return s;
     }

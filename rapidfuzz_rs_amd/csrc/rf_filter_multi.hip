@@ -1,4 +1,4 @@
-// rf_filter_multi.hip -- the candidates within a tight cutoff for Q queries in one pass over the corpus (rf_filter_multi_u32): topk_multi_kernel's
+// rf_filter_multi.hip -- the candidates within a tight cutoff for Q queries in one pass over the corpus (rf_filter_multi_u32, rf_filter_multi_f64): topk_multi_kernel's
 // frame (Q tables side by side in LDS, one candidate per lane, Q recurrence states per lane) with scan_body's early-out schedule, and at a tile's
 // end one compact append per query that still has a passing lane.  Nothing is stored per candidate otherwise.
 // Product code: never includes or links anything from oracle/.
@@ -6,6 +6,7 @@
 
 #include "rf_internal.hpp"
 #include "rf_device.hpp"
+#include "rf_norm_key.hpp"
 
 namespace rf {
 
@@ -21,8 +22,13 @@ namespace rf {
 // Emission: per live member m = ballot(valid && keep); lane 0 adds popcount(m) to the member's counter, the passing lanes store their keys at
 // base + rank while that is below seg_cap.  The counter counts on beyond seg_cap: it is the true number of matches.  Under a tight cutoff
 // passers are rare, so the atomics are (the planner fuses p.early queries only).
+// kNorm (rf_filter_multi_f64): the normalized ops.  p.out_f64 is set, so the looks already run may_pass()'s f64 arithmetic; at a tile's end `keep` is
+// emit_fin's f64 compare to the letter -- nd = dist / maximum against p.cutoff_f64, an arbitrary double -- and never a compare on keys.  What is stored is
+// the key's image of nd, norm_key(dist, maximum) (rf_norm_key.hpp): ascending for both ops (a smaller key is the better score), so topk_desc is not read.
+// f64 cost: the division of the compare is paid per lane, but only by a member that is still live at its tile's end; the maximum is uniform per member
+// and tile, and its scale -- the second f64 division -- is computed behind the ballot, by wavefronts that hold a passer.
 // ---------------------------------------------------------------------------------------------------
-template <class State, int Q, bool kUniform>
+template <class State, int Q, bool kUniform, bool kNorm>
 __global__ __launch_bounds__(kWave* kWavesPerBlock) void filter_multi_kernel(const FilterMultiParams fp)
 {
     using Word = typename State::Word;
@@ -99,16 +105,34 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void filter_multi_kernel(con
         for (int q = 0; q < Q; ++q) {
             if (!(live & (1u << q))) continue;
             const uint32_t raw = st[q].result(p.multi_len1[q], len2);
-            bool keep;
-            const uint32_t v = usize_value(p, fin[q], raw, &keep);
-            const bool pass = valid && keep;
-            const uint64_t m = __ballot(pass);
-            if (m) {
-                uint32_t base = 0;
-                if (lane == 0) base = atomicAdd(fp.count + q * kFilterMultiLine32, (uint32_t)__popcll(m));
-                base = uniform(base);
-                const uint32_t at = base + (uint32_t)__popcll(m & ((1ull << lane) - 1));
-                if (pass && at < fp.seg_cap) fp.cand[(size_t)q * fp.seg_cap + at] = ((uint64_t)(p.topk_desc ? ~v : v) << 32) | idx;
+            if constexpr (!kNorm) {
+                bool keep;
+                const uint32_t v = usize_value(p, fin[q], raw, &keep);
+                const bool pass = valid && keep;
+                const uint64_t m = __ballot(pass);
+                if (m) {
+                    uint32_t base = 0;
+                    if (lane == 0) base = atomicAdd(fp.count + q * kFilterMultiLine32, (uint32_t)__popcll(m));
+                    base = uniform(base);
+                    const uint32_t at = base + (uint32_t)__popcll(m & ((1ull << lane) - 1));
+                    if (pass && at < fp.seg_cap) fp.cand[(size_t)q * fp.seg_cap + at] = ((uint64_t)(p.topk_desc ? ~v : v) << 32) | idx;
+                }
+            } else {
+                // emit_fin's f64 branch, to the letter (has_cutoff: the launcher takes plans under a cutoff only)
+                const uint32_t fmax = uniform(fin[q].max);
+                const uint32_t dist = fin[q].d0 + (uint32_t)p.fin_dR * raw;
+                const double nd = fmax == 0 ? 0.0 : (double)dist / (double)fmax;
+                const bool keep = p.op == RF_OP_NORMALIZED_DISTANCE ? nd <= p.cutoff_f64 : (1.0 - nd) >= p.cutoff_f64;
+                const bool pass = valid && keep;
+                const uint64_t m = __ballot(pass);
+                if (m) {
+                    uint32_t base = 0;
+                    if (lane == 0) base = atomicAdd(fp.count + q * kFilterMultiLine32, (uint32_t)__popcll(m));
+                    base = uniform(base);
+                    const uint32_t at = base + (uint32_t)__popcll(m & ((1ull << lane) - 1));
+                    const double scale = norm_key_scale(fmax);  // (one division per tile and member, wavefront-uniform, behind the ballot)
+                    if (pass && at < fp.seg_cap) fp.cand[(size_t)q * fp.seg_cap + at] = ((uint64_t)norm_key_scaled(dist, fmax, scale) << 32) | idx;
+                }
             }
         }
 
@@ -123,10 +147,15 @@ template <class State, int Q>
 static hipError_t launch_filter_multi_q(const FilterMultiParams& fp, hipStream_t stream, int grid)
 {
     const dim3 g(grid), b(kWave * kWavesPerBlock);
-    if (fp.s.tiles)
-        hipLaunchKernelGGL((filter_multi_kernel<State, Q, false>), g, b, 0, stream, fp);
+    if (fp.norm) {
+        if (fp.s.tiles)
+            hipLaunchKernelGGL((filter_multi_kernel<State, Q, false, true>), g, b, 0, stream, fp);
+        else
+            hipLaunchKernelGGL((filter_multi_kernel<State, Q, true, true>), g, b, 0, stream, fp);
+    } else if (fp.s.tiles)
+        hipLaunchKernelGGL((filter_multi_kernel<State, Q, false, false>), g, b, 0, stream, fp);
     else
-        hipLaunchKernelGGL((filter_multi_kernel<State, Q, true>), g, b, 0, stream, fp);
+        hipLaunchKernelGGL((filter_multi_kernel<State, Q, true, false>), g, b, 0, stream, fp);
     return hipGetLastError();
 }
 template <class State>
@@ -140,10 +169,13 @@ static hipError_t launch_filter_multi_state(const FilterMultiParams& fp, hipStre
 }
 
 // raw: RAW_LEV or RAW_LCS; every query single-word; `narrow` = every query <= 32 symbols.  The grid is scan_grid()'s, as topk_multi_grid's is.
+// fp.norm: an f64 plan of a normalized op under a cutoff, every maximum of the launch <= kNormKeyMaxMaximum (the caller's rule: the launcher cannot see
+// the corpus' lengths).
 hipError_t launch_filter_multi(RawKind raw, bool narrow, const FilterMultiParams& fp, hipStream_t stream)
 {
     const ScanParams& p = fp.s;
     if (!fp.count || (fp.seg_cap && !fp.cand) || p.tile_end > p.n_tiles) return hipErrorInvalidValue;
+    if (fp.norm ? !(p.out_f64 && p.has_cutoff && (p.op == RF_OP_NORMALIZED_DISTANCE || p.op == RF_OP_NORMALIZED_SIMILARITY)) : p.out_f64 != 0) return hipErrorInvalidValue;
     if (p.tile_end <= p.tile_begin) return hipSuccess;
     const int grid = std::max(1, scan_grid(p.tile_end - p.tile_begin));
     if (raw == RAW_LEV) return narrow ? launch_filter_multi_state<Lev32State>(fp, stream, grid) : launch_filter_multi_state<LevState<1>>(fp, stream, grid);

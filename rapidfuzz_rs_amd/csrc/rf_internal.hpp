@@ -195,15 +195,16 @@ int topk_multi_grid(uint32_t tiles);  // workgroups of a launch_topk_multi over 
 hipError_t launch_topk_multi(RawKind raw, bool narrow, const TopkMultiParams& tp, hipStream_t stream);
 hipError_t launch_topk_multi_select(const TopkMultiParams& tp, uint64_t* keys /*[Q][topk_k]*/, hipStream_t stream);
 
-// rf_filter_multi.hip: the candidates within a tight cutoff for Q = 2 / 4 fused queries (rf_filter_multi_u32).  `s` is what topk_multi_kernel reads of it
-// (corpus, finishing coefficients with the cutoff, multi_q / multi_len1 / multi_pm, topk_desc) + tile_begin / tile_end = the union of the members' length
-// windows; everything below is per-call scratch.
+// rf_filter_multi.hip: the candidates within a tight cutoff for Q = 2 / 4 fused queries (rf_filter_multi_u32, rf_filter_multi_f64).  `s` is what
+// topk_multi_kernel reads of it (corpus, finishing coefficients with the cutoff, multi_q / multi_len1 / multi_pm, topk_desc) + tile_begin / tile_end = the
+// union of the members' length windows; everything below is per-call scratch.
 constexpr uint32_t kFilterMultiLine32 = 32;  // u32 units per 128-byte line: one counter per line
 struct FilterMultiParams {
     ScanParams s;
     uint32_t* count;   // [Q] lines, zero at the launch: the member's matches -- ALL of them, also beyond seg_cap
-    uint64_t* cand;    // [Q][seg_cap]: (score or ~score) << 32 | local index of the first seg_cap matches to arrive (nullptr when seg_cap == 0)
+    uint64_t* cand;    // [Q][seg_cap]: (score, ~score or norm_key) << 32 | local index of the first seg_cap matches to arrive (nullptr when seg_cap == 0)
     uint32_t seg_cap;  // entries per member
+    uint32_t norm;     // 1 (rf_filter_multi_f64): s.out_f64 is set, s.op is a normalized op with s.cutoff_f64, and the score image is norm_key(dist, maximum), rf_norm_key.hpp; topk_desc is not read
 };
 hipError_t launch_filter_multi(RawKind raw, bool narrow, const FilterMultiParams& fp, hipStream_t stream);
 

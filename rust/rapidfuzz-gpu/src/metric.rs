@@ -296,6 +296,25 @@ pub(crate) fn topk_multi_f64(cs: &[*const RfComparator], corpus: &crate::Corpus,
     check(unsafe { rf_topk_multi_f64(cs.as_ptr(), q as u32, corpus.0, op, a, k, index_base, score.as_mut_ptr(), idx.as_mut_ptr(), n.as_mut_ptr(), std::ptr::null_mut()) })?;
     Ok((0..q).map(|j| (0..n[j] as usize).map(|m| (idx[j * kk + m], score[j * kk + m])).collect()).collect())
 }
+/// `filter_f64` for a list of comparators in one call (rf_filter_multi_f64): row j is `filter_f64(cs[j], ...)` with indices offset by `index_base`, bit for
+/// bit the same doubles; queries under a tight cutoff share passes over the corpus, 4 (or 2) to a pass.  One repeat with room for the largest count when a
+/// row overflowed.
+pub(crate) fn filter_multi_f64(cs: &[*const RfComparator], corpus: &crate::Corpus, op: c_int, a: &RfArgs, order: c_int, index_base: u64) -> Result<Vec<Vec<(u64, f64)>>, Error> {
+    if cs.is_empty() {
+        return Ok(Vec::new());
+    }
+    let q = cs.len();
+    let mut cap = (corpus.len() / 4096).clamp(64, 1 << 12) as u64;  // (per row, q rows of it: rows under a tight cutoff are short)
+    loop {
+        let (mut idx, mut val, mut n) = (vec![0u64; q * cap as usize], vec![0f64; q * cap as usize], vec![0u64; q]);
+        check(unsafe { rf_filter_multi_f64(cs.as_ptr(), q as u32, corpus.0, op, a, index_base, cap, idx.as_mut_ptr(), val.as_mut_ptr(), n.as_mut_ptr(), order, std::ptr::null_mut()) })?;
+        let most = n.iter().copied().max().unwrap_or(0);
+        if most <= cap {
+            return Ok((0..q).map(|j| (0..n[j] as usize).map(|m| (idx[j * cap as usize + m], val[j * cap as usize + m])).collect()).collect());
+        }
+        cap = most;
+    }
+}
 pub(crate) fn filter_f64(c: *const RfComparator, corpus: &crate::Corpus, op: c_int, a: &RfArgs, order: c_int) -> Result<Vec<(u64, f64)>, Error> {
     let mut cap = (corpus.len() / 64).max(1024) as u64;
     loop {
@@ -443,6 +462,16 @@ macro_rules! usize_metric {
                 pub fn similarity_filter_multi<C: SimilarityCutoff<usize>>(scorers: &[&Self], corpus: &Corpus, args: &Args<usize, C>, order: FilterOrder, index_base: u64) -> Result<Vec<Vec<(u64, usize)>>, Error> {
                     let hs: Vec<*const RfComparator> = scorers.iter().map(|s| s.h as *const RfComparator).collect();
                     filter_multi_u32(&hs, corpus, RF_OP_SIMILARITY, &args.lower(args.score_cutoff.cutoff()), order.lower(), index_base)
+                }
+                /// The candidates within a normalized-distance cutoff for every scorer in one call (rf_filter_multi_f64): row j belongs to `scorers[j]`.
+                pub fn normalized_distance_filter_multi<C: DistanceCutoff<f64>>(scorers: &[&Self], corpus: &Corpus, args: &Args<f64, C>, order: FilterOrder, index_base: u64) -> Result<Vec<Vec<(u64, f64)>>, Error> {
+                    let hs: Vec<*const RfComparator> = scorers.iter().map(|s| s.h as *const RfComparator).collect();
+                    filter_multi_f64(&hs, corpus, RF_OP_NORMALIZED_DISTANCE, &args.lower(args.score_cutoff.cutoff()), order.lower(), index_base)
+                }
+                /// ... and by normalized similarity (at least the cutoff): `normalized_similarity_filter_many` of every scorer.
+                pub fn normalized_similarity_filter_multi<C: SimilarityCutoff<f64>>(scorers: &[&Self], corpus: &Corpus, args: &Args<f64, C>, order: FilterOrder, index_base: u64) -> Result<Vec<Vec<(u64, f64)>>, Error> {
+                    let hs: Vec<*const RfComparator> = scorers.iter().map(|s| s.h as *const RfComparator).collect();
+                    filter_multi_f64(&hs, corpus, RF_OP_NORMALIZED_SIMILARITY, &args.lower(args.score_cutoff.cutoff()), order.lower(), index_base)
                 }
                 /// The k best candidates of every scorer by (normalized distance, index) in one call (rf_topk_multi_f64): row j belongs to `scorers[j]`.
                 pub fn normalized_distance_topk_multi<C: DistanceCutoff<f64>>(scorers: &[&Self], corpus: &Corpus, k: u32, args: &Args<f64, C>, index_base: u64) -> Result<Vec<Vec<(u64, f64)>>, Error> {
