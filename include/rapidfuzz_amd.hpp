@@ -72,9 +72,45 @@ public:
     ~Corpus() { rf_corpus_free(h_); }
     size_t size() const { return rf_corpus_count(h_); }
     const rf_corpus* handle() const { return h_; }
+    /// packed over code points (the u32string_view constructor, or a file saved from such a corpus): read with take_u32
+    bool wide() const { return rf_corpus_is_wide(h_) != 0; }
+    /// The candidates behind the indices a topk / filter call returned -- the `c` of the reference's `for c in corpus`, read back out of the
+    /// packed form: row j is candidate indices[j] - index_base (any order, repeats allowed).
+    std::vector<std::string> take(const std::vector<uint64_t>& indices, uint64_t index_base = 0, void* stream = nullptr) const
+    {
+        return rows<std::string, uint8_t>(rf_corpus_take, indices, index_base, stream);
+    }
+    /// the same as code points: the symbols of a wide corpus, the bytes of a byte corpus zero-extended
+    std::vector<std::u32string> take_u32(const std::vector<uint64_t>& indices, uint64_t index_base = 0, void* stream = nullptr) const
+    {
+        return rows<std::u32string, uint32_t>(rf_corpus_take_u32, indices, index_base, stream);
+    }
+    /// their lengths, in elements
+    std::vector<uint32_t> lengths(const std::vector<uint64_t>& indices, uint64_t index_base = 0, void* stream = nullptr) const
+    {
+        std::vector<uint32_t> out(indices.size());
+        uint32_t none = 0;
+        check(rf_corpus_lengths(h_, indices.empty() ? &index_base : indices.data(), indices.size(), index_base, out.empty() ? &none : out.data(), stream));
+        return out;
+    }
 
 private:
     Corpus() = default;
+    template <class Str, class Elem, class Fn>
+    std::vector<Str> rows(Fn fn, const std::vector<uint64_t>& indices, uint64_t index_base, void* stream) const
+    {
+        // (indices == NULL means "every candidate" in the C ABI: an empty list stays an empty list here)
+        const uint64_t* idx = indices.empty() ? &index_base : indices.data();
+        std::vector<uint64_t> offsets(indices.size() + 1, 0);
+        check(fn(h_, idx, indices.size(), index_base, nullptr, 0, offsets.data(), RF_MEM_HOST, stream));  // the sizing call
+        std::vector<Elem> data(offsets.back());
+        if (!data.empty()) check(fn(h_, idx, indices.size(), index_base, data.data(), data.size(), offsets.data(), RF_MEM_HOST, stream));
+        std::vector<Str> out;
+        out.reserve(indices.size());
+        for (size_t j = 0; j < indices.size(); ++j)
+            out.emplace_back(reinterpret_cast<const typename Str::value_type*>(data.data()) + offsets[j], (size_t)(offsets[j + 1] - offsets[j]));
+        return out;
+    }
     rf_corpus* h_ = nullptr;
 };
 

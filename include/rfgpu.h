@@ -274,9 +274,15 @@ typedef struct rf_host_layout {
     uint32_t n_mixed;      /* the leftovers of every length, sorted by length, share n_mixed MIXED payload blocks of 64 lanes;
                               tiles [n_exact, n_tiles) are the one-length views of those blocks (one per distinct length in a
                               block, same tile_off, orig = 0xFFFFFFFF for the lanes of other lengths) */
+    uint64_t n;            /* candidates the layout was made from */
 } rf_host_layout;
 rf_status rf_corpus_layout_host(const uint8_t *bytes, const uint64_t *offsets, size_t n, rf_host_layout *out);
 void rf_host_layout_free(rf_host_layout *l);
+/* The way back, on the host only: candidate `index` of the input the layout was made from -- writes min(len, capacity) bytes to out (may be NULL when capacity
+ * is 0), *out_len = its length.  The slot is `index` itself when the layout is `identity`, else the one whose orig[] names it; the bytes are found and un-renamed
+ * by the address arithmetic the device kernels of rf_corpus_take use (rapidfuzz_rs_amd/csrc/rf_take_addr.hpp).  A null layout / out_len, a null out with a
+ * capacity, or an index >= n is RF_ERR_INVALID_ARG. */
+rf_status rf_host_layout_candidate(const rf_host_layout *l, uint64_t index, uint8_t *out, uint64_t capacity, uint32_t *out_len);
 size_t rf_corpus_count(const rf_corpus *c);          /* n */
 uint64_t rf_corpus_payload_bytes(const rf_corpus *c); /* sum of candidate lengths */
 uint64_t rf_corpus_device_bytes(const rf_corpus *c);  /* HBM held by the packed form */
@@ -300,6 +306,37 @@ rf_status rf_corpus_slot_index(const rf_corpus *c, uint32_t *out, rf_mem out_mem
  * overflow id. */
 rf_status rf_corpus_pack_u32(const uint32_t *elems, const uint64_t *offsets, size_t n, int device, rf_corpus **out);
 size_t rf_corpus_alphabet_size(const rf_corpus *c, size_t *overflow_symbols);
+
+/* ---- candidates read back out of the packed corpus ----------------------------------------------------
+ * The `c` of the user's `for c in corpus { scorer.distance(c) }` (rapidfuzz-benches/benches/bench_levenshtein.rs:51-60): the reference's loop holds the candidate
+ * itself, every result road of this library returns its INDEX (rf_topk_*, rf_filter_*: `.map(|v| (i, v))`), and the corpus behind the index often exists in packed
+ * form only -- loaded from a file another process packed, packed from device rows, or kept in HBM by a service that dropped its host copy.  The packed form is a
+ * bijection of the input (length buckets, interleaved chunks, renamed symbols, alphabet ids + raw stream); these calls are its inverse, bit for bit.
+ *   rf_corpus_is_wide    1: packed by rf_corpus_pack_u32 (or loaded from such a file): its elements are u32, read with rf_corpus_take_u32
+ *   rf_corpus_lengths    out_len[j] (HOST, m entries) = length of candidate indices[j] - index_base, in elements
+ *   rf_corpus_take       the candidates of a byte corpus; RF_ERR_INVALID_ARG on a wide one
+ *   rf_corpus_take_u32   the candidates as u32 elements: the symbols of a wide corpus, the bytes of a byte corpus zero-extended
+ * Addressing: `indices` is a HOST array of m entries, each index_base + an original candidate index -- the index_base handed to rf_topk_* / rf_filter_*, so a shard's
+ * results can be handed straight back; entries may repeat and come in any order; row j of the output is candidate indices[j] - index_base.  indices == NULL means
+ * every candidate in original order, and m must then equal rf_corpus_count(c).
+ * Outputs: out_offsets is HOST memory, m + 1 entries, always written on success: row j is [out_offsets[j], out_offsets[j + 1]) of the payload, in elements, and
+ * out_offsets[m] is the total.  `capacity` counts the elements out_bytes / out_elems (in out_mem: host or device) has room for.  capacity == 0 is a sizing call: the
+ * payload pointer may be NULL and only out_offsets is written.  capacity != 0 and smaller than the total is RF_ERR_INVALID_ARG with out_offsets valid and the payload
+ * untouched: nothing is ever truncated silently.  An empty candidate is two equal offsets; m == 0 is RF_OK and writes out_offsets[0] = 0.
+ * Errors: a null corpus, a null out_offsets / out_len, a null payload with a non-zero capacity, indices == NULL with m != n, an unknown out_mem or any index outside
+ * [index_base, index_base + n) is RF_ERR_INVALID_ARG -- decided on the host before a device is touched and before anything is written.
+ * How: by index, one work item per row finds its slot (single-length corpora keep original order; a length-bucketed corpus gets a candidate -> slot map on first
+ * use, 4 bytes per candidate, counted in rf_corpus_device_bytes) and length, the host scans the lengths into the offsets, and one lane per (row, 16-symbol chunk)
+ * loads, un-renames and stores; the whole corpus is walked tile by tile like a scan (rf_take.hip).  The calls synchronize `stream` (the total comes home).
+ * Out of scope: device-resident `indices` or offsets; reading candidates out of a corpus FILE that is not loaded; a multi-GPU form (shards are separate calls with
+ * their index_base). */
+int       rf_corpus_is_wide(const rf_corpus *c);
+rf_status rf_corpus_lengths(const rf_corpus *c, const uint64_t *indices, size_t m, uint64_t index_base,
+                            uint32_t *out_len, void *stream);
+rf_status rf_corpus_take(const rf_corpus *c, const uint64_t *indices, size_t m, uint64_t index_base,
+                         uint8_t *out_bytes, uint64_t capacity, uint64_t *out_offsets, rf_mem out_mem, void *stream);
+rf_status rf_corpus_take_u32(const rf_corpus *c, const uint64_t *indices, size_t m, uint64_t index_base,
+                             uint32_t *out_elems, uint64_t capacity, uint64_t *out_offsets, rf_mem out_mem, void *stream);
 
 /* ---- corpus files, corpora larger than HBM (no reference analogue) -----------------------
  * rf_corpus_save / rf_corpus_load: the packed form (header, length table, tile descriptors, slot -> original

@@ -130,6 +130,83 @@ class Corpus:
         N.check(N.lib().rf_corpus_slot_index(self._h, out.ctypes.data, N.MEM_HOST))
         return out
 
+    # ---- the candidates themselves, read back out of the packed form (rf_corpus_take): `corpus[i]` for the i a topk / filter call returned
+    @property
+    def wide(self) -> bool:
+        """True for a corpus over u32 elements (packed by rf_corpus_pack_u32, or loaded from such a file)."""
+        return bool(N.lib().rf_corpus_is_wide(self._h))
+
+    @staticmethod
+    def _indices(indices):
+        """(array kept alive for the call, its address or None = every candidate, entries)"""
+        if indices is None:
+            return None, None, None
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        keep = idx if len(idx) else np.zeros(1, dtype=np.uint64)  # (an empty list is not "every candidate": never a NULL address)
+        return keep, keep.ctypes.data, len(idx)
+
+    def lengths(self, indices=None, index_base: int = 0, stream: Optional[int] = None) -> np.ndarray:
+        """uint32 lengths (in elements) of the candidates `indices` (index_base + original index each), or of all of them."""
+        _keep, ptr, m = self._indices(indices)
+        m = len(self) if m is None else m
+        out = np.empty(m, dtype=np.uint32)
+        N.check(N.lib().rf_corpus_lengths(self._h, ptr, m, index_base, out.ctypes.data, stream))
+        return out
+
+    def take(self, indices=None, index_base: int = 0, device_out: bool = False, stream: Optional[int] = None):
+        """(data, offsets): candidate indices[j] - index_base is data[offsets[j]:offsets[j + 1]]; `indices` may repeat and come in any
+        order, None means every candidate in original order.  data is uint8 for a byte corpus and uint32 for a wide one -- a numpy
+        array, or with device_out a torch tensor on the corpus' device; offsets is a numpy uint64 array of len(indices) + 1."""
+        _keep, ptr, m = self._indices(indices)
+        m = len(self) if m is None else m
+        wide = self.wide
+        fn = N.lib().rf_corpus_take_u32 if wide else N.lib().rf_corpus_take
+        offsets = np.zeros(m + 1, dtype=np.uint64)
+        N.check(fn(self._h, ptr, m, index_base, None, 0, offsets.ctypes.data, N.MEM_HOST, stream))  # the sizing call
+        total = int(offsets[m])
+        if device_out:
+            import torch
+
+            # (4-byte elements travel as int32 and are viewed as uint32 where this torch has the dtype)
+            data = torch.empty(total, dtype=torch.int32 if wide else torch.uint8, device=f"cuda:{self.device}")
+            if total:
+                N.check(fn(self._h, ptr, m, index_base, data.data_ptr(), total, offsets.ctypes.data, N.MEM_DEVICE, stream))
+            if wide and hasattr(torch, "uint32"):
+                data = data.view(torch.uint32)
+            return data, offsets
+        data = np.empty(total, dtype=np.uint32 if wide else np.uint8)
+        if total:
+            N.check(fn(self._h, ptr, m, index_base, data.ctypes.data, total, offsets.ctypes.data, N.MEM_HOST, stream))
+        return data, offsets
+
+    def _rows(self, indices) -> list:
+        data, offsets = self.take(indices)
+        o = offsets.tolist()
+        if self.wide:
+            return [data[o[j]:o[j + 1]].tobytes().decode("utf-32-le", "surrogatepass") for j in range(len(o) - 1)]
+        raw = data.tobytes()
+        return [raw[o[j]:o[j + 1]] for j in range(len(o) - 1)]
+
+    def __getitem__(self, key):
+        """corpus[i] (negative i counts from the end): the candidate as `bytes`, or `str` for a wide corpus; a slice, list or integer
+        array gives a list of those."""
+        n = len(self)
+        if isinstance(key, (int, np.integer)):
+            i = int(key)
+            if not -n <= i < n:
+                raise IndexError(f"candidate {i} of a corpus of {n}")
+            return self._rows([i % n])[0]
+        if isinstance(key, slice):
+            return self._rows(np.arange(*key.indices(n), dtype=np.int64))
+        idx = np.asarray(key, dtype=np.int64).reshape(-1)
+        if len(idx) and (idx.min() < -n or idx.max() >= n):
+            raise IndexError(f"an index lies outside a corpus of {n}")
+        return self._rows(np.where(idx < 0, idx + n, idx))
+
+    def to_list(self) -> list:
+        """Every candidate in original order (`bytes`, or `str` for a wide corpus): the list `from_list` would pack to this corpus."""
+        return self._rows(None)
+
     def save(self, path: str) -> None:
         """Write the packed form to `path` (rf_corpus_save); `Corpus.load` maps it back without re-packing and
         `BatchComparator.stream_many` scans it segment by segment when it does not fit in HBM."""

@@ -633,6 +633,7 @@ try {
     out->identity = L.identity ? 1 : 0;
     out->n_exact = L.n_exact;
     out->n_mixed = (uint32_t)L.mixed.size();
+    out->n = n;
     out->packed = (uint8_t*)std::malloc(std::max<size_t>(1, L.packed_size));
     out->tile_off = (uint64_t*)std::malloc(std::max<size_t>(1, L.tiles.size()) * sizeof(uint64_t));
     out->tile_len = (uint32_t*)std::malloc(std::max<size_t>(1, L.tiles.size()) * sizeof(uint32_t));

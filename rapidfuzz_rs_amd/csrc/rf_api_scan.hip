@@ -571,7 +571,7 @@ static const rf_corpus::GatherMaps* corpus_gather_maps(const rf_corpus* corpus, 
                     if (e == hipSuccess) e = launch_window_table(corpus->d_orig, list.as<uint32_t>(), m.runs, m.rows, m.window_table.as<uint32_t>(), st);
                 }
             }
-            if (e == hipSuccess && !m.window_table.ptr) {
+            if (e == hipSuccess && !m.window_table.ptr && !corpus->accel.take_slot_of.ptr) {  // (rf_corpus_take may have built the same map: adopted below)
                 e = m.slot_of.reserve(corpus->n * sizeof(uint32_t));
                 if (e == hipSuccess) e = hipMemsetAsync(m.slot_of.ptr, 0xFF, corpus->n * sizeof(uint32_t), st);
             }
@@ -582,6 +582,8 @@ static const rf_corpus::GatherMaps* corpus_gather_maps(const rf_corpus* corpus, 
             }
             return e;
         });
+        // one candidate -> slot map per corpus: the buffer moves (its address stays, so a take in flight on another stream keeps reading it)
+        if (maps.slot_ident.ptr && !maps.window_table.ptr && !maps.slot_of.ptr) maps.slot_of = std::move(corpus->accel.take_slot_of);
     }
     return maps.slot_ident.ptr ? &maps : nullptr;
 }

@@ -260,9 +260,11 @@ struct rf_corpus {
         DeviceBuf data6;   // the payload at 6 bits per symbol (the same corpora; ScanParams::data6); tried once
         DeviceBuf len_of;  // candidate -> its length (original order): the normalizing pass of run_many's two-step path
         GatherMaps gather;
+        DeviceBuf take_slot_of;  // candidate -> its slot, for rf_corpus_take / rf_corpus_lengths by index on a length-bucketed corpus (rf_api_take.hip); only while
+                                 // gather.slot_of is not there: the gather path's builder takes this buffer over instead of making a second copy
         bool heads6_tried = false, data6_tried = false;
         uint32_t max_stored_sym = 0xFFFFFFFFu;  // largest stored symbol of the payload, exact; 0xFFFFFFFF = not computed yet (corpus_max_stored_symbol)
-        uint64_t bytes() const { return heads8.bytes() + heads6.bytes() + data6.bytes() + len_of.bytes() + gather.bytes(); }
+        uint64_t bytes() const { return heads8.bytes() + heads6.bytes() + data6.bytes() + len_of.bytes() + gather.bytes() + take_slot_of.bytes(); }
     };
     mutable Accel accel;
     mutable std::mutex scratch_mu;  // guards `accel` and d_sigma_identity (the caches below have their own)

@@ -208,6 +208,29 @@ struct FilterMultiParams {
 };
 hipError_t launch_filter_multi(RawKind raw, bool narrow, const FilterMultiParams& fp, hipStream_t stream);
 
+// rf_take.hip: candidates read back OUT of the packed corpus (rf_corpus_take, rf_corpus_lengths; the addresses: rf_take_addr.hpp).  `s` is what load_tile reads
+// (data, tiles, uniform_len, uniform_tile_bytes) + orig / n / n_tiles for the whole-corpus road; everything below is per-call scratch.
+struct TakeParams {
+    ScanParams s;
+    const uint8_t* inv_sigma;   // 256 bytes: stored symbol -> the candidate's byte (a `char` corpus: -> the symbol's id in the corpus alphabet)
+    const uint32_t* sym_of_id;  // `char` corpora: 256 u32, id -> symbol (kOverflowId's entry is not read when `raw` is there); nullptr = the id is the symbol
+    const void* raw;            // rf_corpus::d_raw (the symbol behind every payload byte, same positions) or nullptr: no overflow symbols
+    uint32_t raw_elem;          // 2 or 4 bytes per raw symbol
+    uint32_t out_u32;           // 1: `out` is uint32_t* (one element per symbol), 0: uint8_t*
+    uint32_t n_slots;           // 64 per tile (a slot beyond it -- a slot map that names no slot for a candidate -- reads as an empty candidate)
+    const uint32_t* slot_of;    // candidate -> slot; nullptr: the slot is the index (single-length corpora keep original order)
+    const uint32_t* idx;        // [m] requested candidates (index_base already taken off, each < n)
+    uint32_t* row_slot;         // [m] take_rows_len_kernel leaves the rows' slots ...
+    uint32_t* row_len;          // [m] ... and lengths here
+    const uint64_t* offsets;    // row j (index road) / candidate i (whole-corpus road) starts at out[offsets[.]], in elements; nullptr (single-length whole-corpus road) = i * uniform_len
+    void* out;
+    uint64_t m;
+    uint32_t row_chunks;        // chunk rows of the longest requested row: take_rows_kernel's items are (row, chunk < row_chunks)
+};
+hipError_t launch_take_rows_len(const TakeParams& p, hipStream_t stream);  // idx -> row_slot, row_len
+hipError_t launch_take_rows(const TakeParams& p, hipStream_t stream);      // row_slot, row_len, offsets -> out
+hipError_t launch_take_all(const TakeParams& p, hipStream_t stream);       // every candidate, walking tiles: offsets -> out
+
 // kernel launchers (rf_scan.hip, rf_long.hip, rf_damerau.hip, rf_jaro.hip, rf_pack.hip)
 hipError_t launch_scan(RawKind raw, const ScanParams& p, hipStream_t stream, int* grid_used);
 hipError_t launch_osa1_asm(const ScanParams& p, hipStream_t stream, int grid);   // the same around the OSA column (OsaState<1>)

@@ -238,7 +238,7 @@ __global__ __launch_bounds__(256) void slot_maps_kernel(const uint32_t* __restri
 {
     for (uint32_t s = blockIdx.x * blockDim.x + threadIdx.x; s < n_slots; s += gridDim.x * blockDim.x) {
         const uint32_t o = orig[s];
-        ident[s] = o == kPad ? kPad : s;
+        if (ident) ident[s] = o == kPad ? kPad : s;  // (nullptr: rf_api_take.hip wants the candidate -> slot map alone)
         if (o != kPad && slot_of) slot_of[o] = s;  // (one-time scattered pass, per corpus; not needed when the window table serves)
     }
 }

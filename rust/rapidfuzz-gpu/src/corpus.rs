@@ -53,6 +53,47 @@ impl Corpus {
         let p = CString::new(path).map_err(|_| Error(RF_ERR_INVALID_ARG, "path contains NUL".into()))?;
         check(unsafe { rf_corpus_save(self.0, p.as_ptr()) })
     }
+    /// Packed over `char`s ([`Corpus::from_chars`], or a file saved from such a corpus): read with [`Corpus::take_chars`].
+    pub fn is_wide(&self) -> bool {
+        unsafe { rf_corpus_is_wide(self.0) != 0 }
+    }
+    /// Lengths, in elements, of the candidates `indices[j] - index_base`.
+    pub fn lengths(&self, indices: &[u64], index_base: u64) -> Result<Vec<u32>, Error> {
+        let mut out = vec![0u32; indices.len()];
+        if !indices.is_empty() {
+            check(unsafe { rf_corpus_lengths(self.0, indices.as_ptr(), indices.len(), index_base, out.as_mut_ptr(), std::ptr::null_mut()) })?;
+        }
+        Ok(out)
+    }
+    /// The candidates behind the indices a top-k / filter call returned -- the `c` of `for c in corpus` -- read back out of the packed
+    /// form: row `j` is candidate `indices[j] - index_base` (any order, repeats allowed).  Byte corpora only.
+    pub fn take(&self, indices: &[u64], index_base: u64) -> Result<Vec<Vec<u8>>, Error> {
+        if indices.is_empty() {
+            return Ok(Vec::new()); // (a NULL list means "every candidate" in the C ABI)
+        }
+        let mut offsets = vec![0u64; indices.len() + 1];
+        let (h, idx, m) = (self.0, indices.as_ptr(), indices.len());
+        check(unsafe { rf_corpus_take(h, idx, m, index_base, std::ptr::null_mut(), 0, offsets.as_mut_ptr(), RF_MEM_HOST, std::ptr::null_mut()) })?;
+        let mut data = vec![0u8; offsets[m] as usize];
+        if !data.is_empty() {
+            check(unsafe { rf_corpus_take(h, idx, m, index_base, data.as_mut_ptr(), data.len() as u64, offsets.as_mut_ptr(), RF_MEM_HOST, std::ptr::null_mut()) })?;
+        }
+        Ok((0..m).map(|j| data[offsets[j] as usize..offsets[j + 1] as usize].to_vec()).collect())
+    }
+    /// The same as `String`s, for a corpus of `char`s (a byte corpus reads as Latin-1: its bytes are the code points 0..255).
+    pub fn take_chars(&self, indices: &[u64], index_base: u64) -> Result<Vec<String>, Error> {
+        if indices.is_empty() {
+            return Ok(Vec::new());
+        }
+        let mut offsets = vec![0u64; indices.len() + 1];
+        let (h, idx, m) = (self.0, indices.as_ptr(), indices.len());
+        check(unsafe { rf_corpus_take_u32(h, idx, m, index_base, std::ptr::null_mut(), 0, offsets.as_mut_ptr(), RF_MEM_HOST, std::ptr::null_mut()) })?;
+        let mut data = vec![0u32; offsets[m] as usize];
+        if !data.is_empty() {
+            check(unsafe { rf_corpus_take_u32(h, idx, m, index_base, data.as_mut_ptr(), data.len() as u64, offsets.as_mut_ptr(), RF_MEM_HOST, std::ptr::null_mut()) })?;
+        }
+        Ok((0..m).map(|j| data[offsets[j] as usize..offsets[j + 1] as usize].iter().map(|&u| char::from_u32(u).unwrap_or(char::REPLACEMENT_CHARACTER)).collect()).collect())
+    }
     pub fn len(&self) -> usize {
         unsafe { rf_corpus_count(self.0) }
     }
