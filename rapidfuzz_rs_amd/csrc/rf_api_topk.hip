@@ -83,7 +83,12 @@ static rf_status topk_core(const rf_comparator* c_in, const rf_corpus* corpus_in
     // RF_TOPK_VIA_SCORES: 0 = never, 1 = default, 2 = every shape with an asm scan (tests).
     static const int via_scores = (int)env_int("RF_TOPK_VIA_SCORES", 1);
     const bool asm_scan = !p.early && !p.band && !p.long_words_pad && p.tile_step == 1 && ((raw == RAW_LEV && p.words <= 4) || (raw == RAW_OSA && p.words == 1));
-    if (asm_scan && (via_scores >= 2 || (via_scores == 1 && raw == RAW_LEV && p.words >= 2))) {
+    const bool scores_road = asm_scan && (via_scores >= 2 || (via_scores == 1 && raw == RAW_LEV && p.words >= 2));
+    const uint32_t kSampleTiles = sw_topk_sample();  // (the sample pass of the in-scan lists, below)
+    const bool sample = !scores_road && kSampleTiles && !p.early && p.tile_end - p.tile_begin >= 8 * kSampleTiles;
+    const bool trace_plan = sw_trace_plan();
+    if (trace_plan) std::fprintf(stderr, "[rf plan] top-k: k=%u words=%u early=%u sample=%d via_scores=%d kept_scores=%d\n", k, p.words, p.early, sample ? 1 : 0, scores_road ? 1 : 0, scores_road && !d_all ? 1 : 0);
+    if (scores_road) {
         uint32_t* d_scores = d_all;
         if (!d_scores) {
             RF_HIP(sc->scores.reserve(corpus->n * sizeof(uint32_t)));
@@ -113,8 +118,7 @@ static rf_status topk_core(const rf_comparator* c_in, const rf_corpus* corpus_in
     // tight cutoff (p.early) the cutoff itself keeps nearly everything out of the lists and the pass is skipped.
     // Each launch selects its own k best in its last workgroup (topk_block_publish): 2 launches, or 1.
     // (RF_TOPK_SAMPLE=<tiles> tunes the sample size, 0 disables the pass: A/B switch)
-    const uint32_t kSampleTiles = sw_topk_sample();
-    if (kSampleTiles && !p.early && p.tile_end - p.tile_begin >= 8 * kSampleTiles) {
+    if (sample) {
         ScanParams ps = p;
         ps.out = nullptr;
         ps.prefill_none = 0;
