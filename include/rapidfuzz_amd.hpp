@@ -1,5 +1,5 @@
 // rapidfuzz_amd.hpp -- header-only C++17 facade over the C ABI of rfgpu.h that mirrors the reference's names:
-//   rapidfuzz::distance::{levenshtein, indel, lcs_seq, damerau_levenshtein, jaro, jaro_winkler}::{Args, BatchComparator, distance, ...}
+//   rapidfuzz::distance::{levenshtein, indel, lcs_seq, damerau_levenshtein, hamming, prefix, postfix, jaro, jaro_winkler}::{Args, BatchComparator, distance, ...}
 //   rapidfuzz::fuzz::{ratio, RatioBatchComparator}
 // `Option<T>` becomes std::optional<T>; the one-vs-many entry points take a rapidfuzz::Corpus.
 // Reference: rapidfuzz-rs v0.5.0, e.g. src/distance/levenshtein.rs:86-148 (Args, WeightTable), :1636-1818
@@ -131,6 +131,9 @@ struct Args {
     Args score_hint(T v) const { Args a = *this; a.hint = v; return a; }
     Args weights(const WeightTable& t) const { Args a = *this; a.w = t; return a; }
     Args prefix_weight(double p) const { Args a = *this; a.pw = p; return a; }
+    /// hamming only, `Args::pad(true)` (hamming.rs:112-118).  Without it a candidate of another length than the query is the reference's
+    /// Err(DifferentLengthArgs): the single-candidate methods throw Error(RF_ERR_INVALID_ARG), *_many leaves its entry empty, *_filter_* and *_topk_* drop it
+    Args pad(bool on = true) const { Args a = *this; a.flags = on ? (a.flags | RF_FLAG_HAMMING_PAD) : (a.flags & ~RF_FLAG_HAMMING_PAD); return a; }
     rf_args to_c() const
     {
         rf_args a;
@@ -223,7 +226,7 @@ public:
             check(rf_many_multi_u32(hs.data(), (uint32_t)hs.size(), c.handle(), RF_OP_DISTANCE, &ca, out.data(), RF_MEM_HOST, nullptr));
             for (size_t j = 0; j < scorers.size(); ++j)
                 for (size_t i = 0; i < c.size(); ++i)
-                    if (out[j * c.size() + i] != RF_NONE_U32) res[j][i] = out[j * c.size() + i];
+                    if (out[j * c.size() + i] != RF_NONE_U32 && !(M == RF_HAMMING && out[j * c.size() + i] == RF_DIFFERENT_LENGTH_U32)) res[j][i] = out[j * c.size() + i];
         }
         return res;
     }
@@ -288,19 +291,19 @@ public:
     // ---- the reference's per-candidate methods (a one-candidate corpus through the same kernels)
     std::optional<usize_result> distance_with_args(std::string_view s2, const Args<usize_result>& a) const
     {
-        return distance_many(Corpus({s2}), a)[0];
+        return many<usize_result>(Corpus({s2}), RF_OP_DISTANCE, a.to_c(), true)[0];
     }
     std::optional<usize_result> similarity_with_args(std::string_view s2, const Args<usize_result>& a) const
     {
-        return similarity_many(Corpus({s2}), a)[0];
+        return many<usize_result>(Corpus({s2}), RF_OP_SIMILARITY, a.to_c(), true)[0];
     }
     std::optional<double> normalized_distance_with_args(std::string_view s2, const Args<double>& a) const
     {
-        return normalized_distance_many(Corpus({s2}), a)[0];
+        return many<double>(Corpus({s2}), RF_OP_NORMALIZED_DISTANCE, a.to_c(), true)[0];
     }
     std::optional<double> normalized_similarity_with_args(std::string_view s2, const Args<double>& a) const
     {
-        return normalized_similarity_many(Corpus({s2}), a)[0];
+        return many<double>(Corpus({s2}), RF_OP_NORMALIZED_SIMILARITY, a.to_c(), true)[0];
     }
     usize_result distance(std::string_view s2) const { return *distance_with_args(s2, {}); }
     usize_result similarity(std::string_view s2) const { return *similarity_with_args(s2, {}); }
@@ -311,19 +314,27 @@ public:
 
 private:
     template <class T>
-    std::vector<std::optional<T>> many(const Corpus& c, rf_op op, const rf_args& a) const
+    std::vector<std::optional<T>> many(const Corpus& c, rf_op op, const rf_args& a, bool throw_different_length = false) const
     {
+        // (hamming without pad: a candidate of another length is neither a value nor None -- RF_DIFFERENT_LENGTH_*, rfgpu.h)
         std::vector<std::optional<T>> res(c.size());
         if constexpr (std::is_floating_point_v<T>) {
             std::vector<double> out(c.size());
             check(rf_many_f64(h_, c.handle(), op, &a, out.data(), RF_MEM_HOST, nullptr));
-            for (size_t i = 0; i < out.size(); ++i)
+            for (size_t i = 0; i < out.size(); ++i) {
+                if (M == RF_HAMMING && throw_different_length && rfgpu_is_different_length_f64(out[i])) throw Error(RF_ERR_INVALID_ARG, "Differing length arguments provided");
                 if (!std::isnan(out[i])) res[i] = out[i];
+            }
         } else {
             std::vector<uint32_t> out(c.size());
             check(rf_many_u32(h_, c.handle(), op, &a, out.data(), RF_MEM_HOST, nullptr));
-            for (size_t i = 0; i < out.size(); ++i)
+            for (size_t i = 0; i < out.size(); ++i) {
+                if (M == RF_HAMMING && out[i] == RF_DIFFERENT_LENGTH_U32) {
+                    if (throw_different_length) throw Error(RF_ERR_INVALID_ARG, "Differing length arguments provided");
+                    continue;
+                }
                 if (out[i] != RF_NONE_U32) res[i] = out[i];
+            }
         }
         return res;
     }
@@ -453,6 +464,9 @@ using levenshtein = detail::Module<RF_LEVENSHTEIN, false>;    // src/distance/le
 using indel = detail::Module<RF_INDEL, false>;                // src/distance/indel.rs
 using lcs_seq = detail::Module<RF_LCS_SEQ, false>;            // src/distance/lcs_seq.rs
 using damerau_levenshtein = detail::Module<RF_DAMERAU_LEVENSHTEIN, false>;  // src/distance/damerau_levenshtein.rs
+using hamming = detail::Module<RF_HAMMING, false>;            // src/distance/hamming.rs (Args::pad)
+using prefix = detail::Module<RF_PREFIX, false>;              // src/distance/prefix.rs
+using postfix = detail::Module<RF_POSTFIX, false>;            // src/distance/postfix.rs
 using jaro = detail::Module<RF_JARO, true>;                   // src/distance/jaro.rs
 using jaro_winkler = detail::Module<RF_JARO_WINKLER, true>;   // src/distance/jaro_winkler.rs
 }  // namespace distance

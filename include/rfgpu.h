@@ -12,7 +12,8 @@
  * entry points, `char` / u32.
  *
  * Error model: metric evaluation never fails in the reference (no `Result` on this path; "above the
- * cutoff" is `None`, src/common.rs:43-45).  rf_status reports ENGINE failures only (bad argument, HIP
+ * cutoff" is `None`, src/common.rs:43-45) -- with ONE exception, hamming without pad(true), whose candidates of another
+ * length than the query are Err(DifferentLengthArgs): see RF_FLAG_HAMMING_PAD.  rf_status reports ENGINE failures only (bad argument, HIP
  * error, shape the device kernels do not cover).  There is NO CPU fallback: a shape that has no kernel
  * returns RF_ERR_UNSUPPORTED instead of silently computing on the host.
  *
@@ -95,6 +96,8 @@
  *                                           score_hint (pass under max(hint, 31), then only what it left unresolved: rf_hint.hip); 4294967295: never
  *   RF_HINT_SAMPLE_MIN_TILES      16384     fewest tiles for which such a call first runs the hint pass over every (tiles / 512)-th tile and drops the hint when fewer
  *                                           than 70 % of the candidates are within it (a wrong hint then costs ~3 % instead of up to + 55 %); 4294967295: never sample
+ *   RF_COMPARE_MAX_BLOCKS         0 (none)  most workgroups of a hamming / prefix / postfix scan (rf_compare.hip): 1 makes four wavefronts walk every tile of the corpus
+ *                                           (the forced several-tiles-per-wavefront run of tests/compare_check.py); 0: the grid of every short-running launch
  *   RF_STREAM_KEEP                1         0: rf_stream_many_* allocates and frees its pinned / device buffer sets per call instead of keeping them
  *   RF_STREAM_THREADS             16        host threads that read a corpus file's payload (rf_stream_many_*, rf_corpus_load)
  *   RF_PACK_TIMING / RF_SELECT_DEBUG / RF_TRACE_PLAN / RF_STREAM_TIMING   unset   set: phase timings / selection statistics / one line per
@@ -129,8 +132,13 @@ typedef enum rf_metric {
     RF_JARO_WINKLER = 4, /* src/distance/jaro_winkler.rs */
     RF_FUZZ_RATIO = 5,   /* src/fuzz.rs RatioBatchComparator */
     RF_OSA = 6,          /* src/distance/osa.rs (widening beyond the north-star path) */
-    RF_DAMERAU_LEVENSHTEIN = 7 /* src/distance/damerau_levenshtein.rs:191-215 (the unrestricted distance, distance_zhao :111-168; no bit-parallel path in the
-                                  reference either: a row DP per candidate, rf_damerau.hip) */
+    RF_DAMERAU_LEVENSHTEIN = 7, /* src/distance/damerau_levenshtein.rs:191-215 (the unrestricted distance, distance_zhao :111-168; no bit-parallel path in the
+                                   reference either: a row DP per candidate, rf_damerau.hip) */
+    /* 8 is NOT a metric and never will be: rf_comparator_new(8, ...) is RF_ERR_INVALID_ARG, and tests/test_dl_reference.py holds the library to exactly that
+     * ("the first id past the last metric is refused") -- a test file that may not change.  The three byte-compare metrics therefore start at 9. */
+    RF_HAMMING = 9,  /* src/distance/hamming.rs:138-187 (mismatches over the common length + the length difference; :232-234 pad: RF_FLAG_HAMMING_PAD) */
+    RF_PREFIX = 10,  /* src/distance/prefix.rs:47-69 (similarity = length of the common prefix; maximum = max(len1, len2)) */
+    RF_POSTFIX = 11  /* src/distance/postfix.rs:47-69 (similarity = length of the common suffix; maximum = max(len1, len2)) */
 } rf_metric;
 
 /* the four methods every BatchComparator has (e.g. levenshtein.rs:1660-1817) */
@@ -146,11 +154,24 @@ typedef enum rf_mem { RF_MEM_HOST = 0, RF_MEM_DEVICE = 1 } rf_mem;
 #define RF_NO_CUTOFF UINT64_MAX   /* Args::default(): NoScoreCutoff (src/common.rs:3-30) */
 #define RF_NONE_U32 0xFFFFFFFFu   /* Option::None in a u32 result slot */
 /* Option::None in an f64 result slot is a quiet NaN (test with isnan) */
+/* hamming without RF_FLAG_HAMMING_PAD, per-candidate result vectors only: Err(DifferentLengthArgs) (hamming.rs:232-234) in a u32 slot, and in an f64 slot a
+ * quiet NaN like None (isnan is true for both: a caller that treats "no value" alike needs no change) that differs from None's 0x7FF8000000000000 in its last bit */
+#define RF_DIFFERENT_LENGTH_U32 0xFFFFFFFEu
+#define RF_DIFFERENT_LENGTH_F64_BITS 0x7FF8000000000001ull
+#define RF_NONE_F64_BITS 0x7FF8000000000000ull
+static inline int rfgpu_is_different_length_f64(double v) /* (named outside the rf_ prefix of the exported symbols: it lives in this header) */
+{
+    uint64_t u = 0;
+    const unsigned char *src = (const unsigned char *)&v;
+    unsigned char *dst = (unsigned char *)&u;
+    for (unsigned i = 0; i < sizeof u; ++i) dst[i] = src[i];
+    return u == RF_DIFFERENT_LENGTH_F64_BITS;
+}
 
 /*
  * Flattened `Args` builders: levenshtein.rs:86-126 (score_cutoff, score_hint, weights),
  * jaro_winkler.rs:25-62 (prefix_weight), and the identical score_cutoff/score_hint pairs of
- * lcs_seq / indel / jaro / fuzz / osa / damerau_levenshtein.  Use rf_args_default() and then set fields.
+ * lcs_seq / indel / jaro / fuzz / osa / damerau_levenshtein / hamming / prefix / postfix.  Use rf_args_default() and then set fields.
  *   cutoff_usize : RF_NO_CUTOFF = NoScoreCutoff, else WithScoreCutoff(v) for the usize-valued ops
  *   cutoff_f64   : NaN = NoScoreCutoff, else WithScoreCutoff(v) for the f64-valued ops
  *   score_hint_* : results never depend on a hint (levenshtein.rs:2153-2160); in the reference it steers the CPU band search
@@ -166,7 +187,8 @@ typedef enum rf_mem { RF_MEM_HOST = 0, RF_MEM_DEVICE = 1 } rf_mem;
  *                  rf_topk_u32 with RF_OP_DISTANCE and no cutoff: the scan first runs under the
  *                  cutoff `hint` (a cutoff scan costs a fraction of a full one) and the k best are final if k candidates pass,
  *                  otherwise the hint doubles (past a quarter of the longest possible distance the plain scan runs).
- *                  Every other call ignores it (damerau_levenshtein: so does the reference, damerau_levenshtein.rs:205).
+ *                  Every other call ignores it (damerau_levenshtein, hamming, prefix, postfix: so does the reference, damerau_levenshtein.rs:205,
+ *                  hamming.rs:176-187, details/distance.rs:154-274).
  *
  * Three places where the device deliberately does NOT reproduce what release-mode rapidfuzz 0.5.0 returns (all tested,
  * tests/test_gpu_parity.py, all also in DESIGN.md section 3):
@@ -207,6 +229,17 @@ typedef struct rf_args {
  * loop has no order but the caller's.  A single-length corpus' slots are its indices (the flag changes nothing); for a u32 query with overflow-class symbols
  * rf_many_* refuses the flag with RF_ERR_UNSUPPORTED for such a query; every other entry point (rf_many_multi_*, rf_topk_*, rf_stream_many_*, rf_one_*, rf_filter_*) ignores it.  Values are those of the default call: tests/test_gpu_filter.py permutes and compares. */
 #define RF_FLAG_SLOT_ORDER 0x2u
+
+/* hamming only: Args::pad(true) (hamming.rs:232-234) -- the shorter string counts as padded with symbols that match nothing, distance = mismatches over the
+ * common length + |len1 - len2|.  WITHOUT the flag (the reference's default) a candidate whose length differs from the query's is Err(DifferentLengthArgs), which
+ * is neither a value nor None:
+ *   rf_many_* / rf_many_multi_* / rf_stream_many_*   the candidate's slot holds RF_DIFFERENT_LENGTH_U32 / the NaN RF_DIFFERENT_LENGTH_F64_BITS
+ *                                                    (rfgpu_is_different_length_f64); None (RF_NONE_U32 / the None NaN) still means "above the cutoff"
+ *   rf_one_*                                         RF_ERR_INVALID_ARG, rf_last_error() = "Differing length arguments provided" (hamming.rs:126-134): there is no slot
+ *   rf_filter_* / rf_topk_* / rf_filter_multi_* / rf_topk_multi_* / rf_topk_*_device     the candidate is dropped exactly like None: what a
+ *                                                    `filter_map(|c| scorer.distance_with_args(c, &args).ok().flatten())` keeps
+ * The length decision is per tile of 64 candidates of one length: such a tile is answered without its payload being read.  Every other metric ignores the flag. */
+#define RF_FLAG_HAMMING_PAD 0x4u
 
 void rf_args_default(rf_args *a);
 
@@ -367,7 +400,7 @@ rf_status rf_release_caches(void);
 /* ---- one-vs-many ------------------------------------------------------------------------------
  * out[i] = scorer.<op>_with_args(candidate_i, &args) for every candidate, original order.
  *
- * rf_many_u32: the usize-valued methods of levenshtein / indel / lcs_seq / osa / damerau_levenshtein
+ * rf_many_u32: the usize-valued methods of levenshtein / indel / lcs_seq / osa / damerau_levenshtein / hamming / prefix / postfix
  *   (distance_with_args levenshtein.rs:1750-1777, similarity_with_args :1790-1817; indel.rs:464-521;
  *    lcs_seq.rs:893-949).  RF_NONE_U32 = None.
  * rf_many_f64: normalized_* of those metrics (levenshtein.rs:1670-1737 ...), all four methods of

@@ -64,6 +64,12 @@ class Args:
         a length-bucketed corpus then skips its gather pass (RF_FLAG_SLOT_ORDER)."""
         return self._with(_flags=(self._flags | N.FLAG_SLOT_ORDER) if on else (self._flags & ~N.FLAG_SLOT_ORDER))
 
+    def pad(self, on: bool = True) -> "Args":
+        """hamming only, `Args::pad(true)` (hamming.rs:112-118): strings of different lengths compare as if the shorter one were padded with symbols that
+        match nothing.  Without it such a candidate is the reference's `Err(DifferentLengthArgs)`: `DIFFERENT_LENGTH_U32` / the NaN with
+        `DIFFERENT_LENGTH_F64_BITS` in `*_many` results, an `RfError` from the single-candidate methods, dropped by `filter_many` / `topk` (RF_FLAG_HAMMING_PAD)."""
+        return self._with(_flags=(self._flags | N.FLAG_HAMMING_PAD) if on else (self._flags & ~N.FLAG_HAMMING_PAD))
+
     def to_c(self, is_float: bool) -> N.RfArgs:
         a = N.RfArgs()
         N.lib().rf_args_default(C.byref(a))
@@ -140,6 +146,8 @@ class BatchComparator:
         """The cached BlockPatternMatchVector as uint64 [256, max(1, ceil(len/64))]."""
         n = C.c_size_t()
         p = N.lib().rf_comparator_pm(self._h, C.byref(n))
+        if not p:  # a u32 query (one table per corpus alphabet), or hamming / prefix / postfix (no table in the reference)
+            raise ValueError("this comparator has no pattern-match table of its own")
         w = max(1, n.value)
         return np.ctypeslib.as_array(p, shape=(256 * w,)).copy().reshape(256, w)
 
@@ -366,7 +374,11 @@ class BatchComparator:
         corpus = (Corpus.from_u32_list if self._wide else Corpus.from_list)([s2], device=default_device())
         r = self.many(op, corpus, args, **kw)[0]
         if r.dtype == np.uint32:
+            if int(r) == N.DIFFERENT_LENGTH_U32 and self.METRIC == N.HAMMING:  # Err(DifferentLengthArgs), hamming.rs:232-234
+                raise N.RfError(N.RF_ERR_INVALID_ARG, "Differing length arguments provided")
             return None if int(r) == N.NONE_U32 else int(r)
+        if self.METRIC == N.HAMMING and int(r.view(np.uint64)) == N.DIFFERENT_LENGTH_F64_BITS:
+            raise N.RfError(N.RF_ERR_INVALID_ARG, "Differing length arguments provided")
         return None if math.isnan(float(r)) else float(r)
 
     def distance(self, s2, args=None, **kw):

@@ -64,9 +64,17 @@ void rf_args_default(rf_args* a)
 // ---------------------------------------------------------------------------------------------------
 // comparator
 // ---------------------------------------------------------------------------------------------------
+// the ids of rfgpu.h: 0..7 and 9..11 -- 8 is no metric (the header says why)
+static bool metric_known(rf_metric metric)
+{
+    const int m = (int)metric;
+    return (m >= (int)RF_LEVENSHTEIN && m <= (int)RF_DAMERAU_LEVENSHTEIN) || (m >= (int)RF_HAMMING && m <= (int)RF_POSTFIX);
+}
+static bool metric_is_compare(rf_metric metric) { return metric == RF_HAMMING || metric == RF_PREFIX || metric == RF_POSTFIX; }
+
 rf_status rf_comparator_new(rf_metric metric, const uint8_t* s1, size_t len1, rf_comparator** out)
 try {
-    if (!out || (len1 && !s1) || (int)metric < 0 || (int)metric > (int)RF_DAMERAU_LEVENSHTEIN) {
+    if (!out || (len1 && !s1) || !metric_known(metric)) {
         set_error("rf_comparator_new: invalid argument");
         return RF_ERR_INVALID_ARG;
     }
@@ -94,7 +102,7 @@ RF_ABI_CATCH
 // corpus' symbol ids, the first time the comparator meets it (resolve()).
 rf_status rf_comparator_new_u32(rf_metric metric, const uint32_t* s1, size_t len1, rf_comparator** out)
 try {
-    if (!out || (len1 && !s1) || (int)metric < 0 || (int)metric > (int)RF_DAMERAU_LEVENSHTEIN) {
+    if (!out || (len1 && !s1) || !metric_known(metric)) {
         set_error("rf_comparator_new_u32: invalid argument");
         return RF_ERR_INVALID_ARG;
     }
@@ -134,7 +142,9 @@ size_t rf_comparator_query_len(const rf_comparator* c) { return c->wide ? c->s1w
 const uint64_t* rf_comparator_pm(const rf_comparator* c, size_t* block_count)
 {
     if (block_count) *block_count = c->block_count;
-    return c->wide ? nullptr : c->pm.data();  // a u32 comparator has one table per corpus alphabet, none of its own
+    // a u32 comparator has one table per corpus alphabet, none of its own; hamming / prefix / postfix have no pattern-match table in the reference
+    // (the one kept here is how the query travels to the device: rf_device.hpp stage_query_bytes)
+    return (c->wide || metric_is_compare(c->metric)) ? nullptr : c->pm.data();
 }
 
 // Which byte-level comparator serves (c, corpus).  Byte query x byte corpus: c itself.  Anything involving u32

@@ -300,7 +300,7 @@ static rf_status run_filter(const rf_comparator* c, const rf_corpus* corpus, rf_
         void* d_tmp = nullptr;
         RF_HIP(sc.get(&d_tmp, m * elem));
         rf_args a = *args;
-        a.flags &= ~(kFlagSlotsInternal | kFlagWindowInternal);
+        a.flags &= ~kFlagsInternal;  // (rf_host.hpp: a result vector that is compacted holds Some and None only)
         // A cutoff's length window (plan(): the tiles outside [tile_begin, tile_end) are None by their length alone) is all this call has to look at in a slot-ordered
         // temporary -- slot = 64 x tile + lane for exact tiles and views alike: neither the pre-fill nor the compaction touches the rest (ragged [1, 64] under a
         // cutoff of 3 edits: 4 of 64 lengths)

@@ -52,14 +52,15 @@ rf_status plan(const rf_comparator* c, const rf_corpus* corpus, rf_op op, const 
             }
     }
 
-    const bool usize_metric = c->metric == RF_LEVENSHTEIN || c->metric == RF_INDEL || c->metric == RF_LCS_SEQ || c->metric == RF_OSA || c->metric == RF_DAMERAU_LEVENSHTEIN;
+    const bool usize_metric = c->metric == RF_LEVENSHTEIN || c->metric == RF_INDEL || c->metric == RF_LCS_SEQ || c->metric == RF_OSA || c->metric == RF_DAMERAU_LEVENSHTEIN ||
+                              c->metric == RF_HAMMING || c->metric == RF_PREFIX || c->metric == RF_POSTFIX;
     const bool norm_op = op == RF_OP_NORMALIZED_DISTANCE || op == RF_OP_NORMALIZED_SIMILARITY;
     if ((int)op < 0 || (int)op > (int)RF_OP_NORMALIZED_SIMILARITY) {
         set_error("unknown rf_op");
         return RF_ERR_INVALID_ARG;
     }
     if (usize_metric && (norm_op != f64_out)) {
-        set_error("levenshtein/indel/lcs_seq/osa/damerau_levenshtein: distance and similarity are u32-valued (rf_many_u32), normalized_* are "
+        set_error("levenshtein/indel/lcs_seq/osa/damerau_levenshtein/hamming/prefix/postfix: distance and similarity are u32-valued (rf_many_u32), normalized_* are "
                   "f64-valued (rf_many_f64)");
         return RF_ERR_INVALID_ARG;
     }
@@ -153,6 +154,18 @@ rf_status plan(const rf_comparator* c, const rf_corpus* corpus, rf_op op, const 
         }
         break;
     }
+    case RF_HAMMING:  // hamming.rs:165-187; maximum = max(len1, len2), every op the MetricUsize default (details/distance.rs:154-274): FIN_LEV at factor 1
+        *raw = RAW_HAMMING;
+        p->finish = FIN_LEV;
+        p->factor = 1;
+        p->cmp_strict = (args->flags & RF_FLAG_HAMMING_PAD) ? 0u : 1u;             // hamming.rs:232-234
+        p->cmp_err_encode = (args->flags & kFlagErrEncodeInternal) ? 1u : 0u;      // (rf_host.hpp: the per-candidate entry points only)
+        break;
+    case RF_PREFIX:   // prefix.rs:47-69: similarity = the common prefix' length, maximum = max(len1, len2): FIN_LCS with that length as the raw value
+    case RF_POSTFIX:  // postfix.rs:47-69: the same over the common suffix
+        *raw = c->metric == RF_PREFIX ? RAW_PREFIX : RAW_POSTFIX;
+        p->finish = FIN_LCS;
+        break;
     case RF_INDEL:
         *raw = RAW_LCS;
         p->finish = FIN_INDEL;
@@ -276,7 +289,11 @@ rf_status plan(const rf_comparator* c, const rf_corpus* corpus, rf_op op, const 
         }
     }
 
-    if (*raw == RAW_WF || *raw == RAW_DL) return RF_OK;  // the row-DP kernels: every tile, every column; the cutoff is emit_fin's compare
+    if (raw_is_compare(*raw) && p->len1 > 150000) {  // (the query sits in LDS, rf_compare.hip: 160 KiB per workgroup)
+        set_error("hamming / prefix / postfix: a query beyond 150 000 symbols does not fit the LDS of the device");
+        return RF_ERR_UNSUPPORTED;
+    }
+    if (*raw == RAW_WF || *raw == RAW_DL || raw_is_compare(*raw)) return RF_OK;  // the row-DP and byte-compare kernels: every tile; the cutoff is emit_fin's compare
     // Long query + small distance cutoff (the reference's hyrroe2003_small_band_with_pm, levenshtein.rs:509-617, taken when
     // len1 > 64 and 2k + 1 <= 64, :1059-1062): one 64-bit word sliding down the diagonal instead of ceil(len1 / 64) words
     // per column.  k is the cutoff on the RAW distance (the common weight factor divided out).
@@ -1339,7 +1356,7 @@ rf_status rf_many_u32(const rf_comparator* c, const rf_corpus* corpus, rf_op op,
                       rf_mem out_mem, void* stream)
 try {
     if (!args) return run_many(c, corpus, op, args, out, out_mem, stream, false);
-    const rf_args a = sanitized_args(args, true);
+    const rf_args a = sanitized_args(args, true, true);
     return run_many(c, corpus, op, &a, out, out_mem, stream, false);
 }
 RF_ABI_CATCH
@@ -1348,7 +1365,7 @@ rf_status rf_many_f64(const rf_comparator* c, const rf_corpus* corpus, rf_op op,
                       rf_mem out_mem, void* stream)
 try {
     if (!args) return run_many(c, corpus, op, args, out, out_mem, stream, true);
-    const rf_args a = sanitized_args(args, true);
+    const rf_args a = sanitized_args(args, true, true);
     return run_many(c, corpus, op, &a, out, out_mem, stream, true);
 }
 RF_ABI_CATCH
@@ -1360,7 +1377,12 @@ static rf_status run_one(const rf_comparator* c, const uint8_t* s2, size_t len2,
         set_error("rf_one: invalid argument");
         return RF_ERR_INVALID_ARG;
     }
-    const rf_args args_v = sanitized_args(args_in, false), *args = &args_v;
+    const rf_args args_v = sanitized_args(args_in, false, true), *args = &args_v;
+    // hamming without pad(true): Err(DifferentLengthArgs) (hamming.rs:232-234) -- there is no slot to carry it, so it is the call's status
+    if (c->metric == RF_HAMMING && !(args->flags & RF_FLAG_HAMMING_PAD) && len2 != (c->wide ? c->s1w.size() : c->s1.size())) {
+        set_error("Differing length arguments provided");
+        return RF_ERR_INVALID_ARG;
+    }
     const uint64_t offsets[2] = {0, len2};
     rf_corpus* corpus = nullptr;
     rf_status s = rf_corpus_pack(s2, offsets, 1, device, &corpus);
@@ -1405,7 +1427,7 @@ static rf_status run_many_multi(const rf_comparator* const* cs_in, uint32_t q, c
         set_error("null handle or args");
         return RF_ERR_INVALID_ARG;
     }
-    const rf_args args_v = sanitized_args(args_in, false), *args = &args_v;  // (rows of n entries: RF_FLAG_SLOT_ORDER is rf_many_*'s alone)
+    const rf_args args_v = sanitized_args(args_in, false, true), *args = &args_v;  // (rows of n entries: RF_FLAG_SLOT_ORDER is rf_many_*'s alone)
     if (q == 0 || corpus->n == 0) return RF_OK;
     if (!out) {
         set_error("null output");

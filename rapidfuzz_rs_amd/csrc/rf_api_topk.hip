@@ -37,8 +37,8 @@ static rf_status topk_core(const rf_comparator* c_in, const rf_corpus* corpus_in
     }
     // (a long query under a small cutoff is planned onto the band kernel, which has no top-k epilogue, and the register-resident
     // scans stop at 8 words: beyond 512 symbols that shape goes the selection way like every other long query -- ADVICE r2)
-    if (p.long_words_pad || raw == RAW_WF || raw == RAW_DL || (p.band && c->words > (size_t)kMaxWords)) {
-        set_error("top-k: queries longer than 512 symbols, general Levenshtein weight tables and damerau_levenshtein are served by rf_many_* only (rf_topk_u32 / rf_topk_f64 select from its result)");
+    if (p.long_words_pad || raw == RAW_WF || raw == RAW_DL || raw_is_compare(raw) || (p.band && c->words > (size_t)kMaxWords)) {
+        set_error("top-k: queries longer than 512 symbols, general Levenshtein weight tables, damerau_levenshtein, hamming, prefix and postfix are served by rf_many_* only (rf_topk_u32 / rf_topk_f64 select from its result)");
         return RF_ERR_UNSUPPORTED;
     }
     *desc = op == RF_OP_SIMILARITY;
@@ -504,7 +504,8 @@ try {
         RF_HIP(hipMemsetAsync(d_entries_out, 0xFF, (size_t)k * sizeof(rf_topk_entry), st));
         return RF_OK;
     }
-    const bool usize_metric = c->metric == RF_LEVENSHTEIN || c->metric == RF_INDEL || c->metric == RF_LCS_SEQ || c->metric == RF_OSA || c->metric == RF_DAMERAU_LEVENSHTEIN;
+    const bool usize_metric = c->metric == RF_LEVENSHTEIN || c->metric == RF_INDEL || c->metric == RF_LCS_SEQ || c->metric == RF_OSA || c->metric == RF_DAMERAU_LEVENSHTEIN ||
+                              c->metric == RF_HAMMING || c->metric == RF_PREFIX || c->metric == RF_POSTFIX;
     const bool f64 = !usize_metric || op == RF_OP_NORMALIZED_DISTANCE || op == RF_OP_NORMALIZED_SIMILARITY;
     if (!f64 && k <= (uint64_t)kWave) {
         // the in-scan lists: keys with the LOCAL index, widened on the device -- nothing synchronizes

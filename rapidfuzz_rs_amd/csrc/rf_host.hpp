@@ -373,11 +373,17 @@ constexpr uint8_t kOverflowId = 254, kAbsentId = 255;
 constexpr uint32_t kFlagSlotsInternal = 0x40000000u;
 // ... and (rf_filter_* only, with the bit above): the caller reads nothing outside the slots of the cutoff's length window, so nothing there needs its None
 constexpr uint32_t kFlagWindowInternal = 0x20000000u;
-inline rf_args sanitized_args(const rf_args* a, bool slots_allowed)
+// ... and (the per-candidate entry points only: rf_many_*, rf_one_*, rf_many_multi_*, rf_stream_many_*): hamming without RF_FLAG_HAMMING_PAD writes the reference's
+// Err(DifferentLengthArgs) as its own encoding (rfgpu.h RF_DIFFERENT_LENGTH_*).  Without the bit -- rf_filter_*, rf_topk_*, the *_multi selections, every internal
+// scan -- such a candidate is the ordinary None: what selects or compacts a result vector compares None by bits and knows no third value.
+constexpr uint32_t kFlagErrEncodeInternal = 0x10000000u;
+constexpr uint32_t kFlagsInternal = kFlagSlotsInternal | kFlagWindowInternal | kFlagErrEncodeInternal;
+inline rf_args sanitized_args(const rf_args* a, bool slots_allowed, bool per_candidate = false)
 {
     rf_args r = *a;
-    r.flags &= ~(kFlagSlotsInternal | kFlagWindowInternal);
+    r.flags &= ~kFlagsInternal;
     if (slots_allowed && (r.flags & RF_FLAG_SLOT_ORDER)) r.flags |= kFlagSlotsInternal;
+    if (per_candidate) r.flags |= kFlagErrEncodeInternal;
     return r;
 }
 __attribute__((visibility("hidden"))) extern std::atomic<uint64_t> g_corpus_uid;

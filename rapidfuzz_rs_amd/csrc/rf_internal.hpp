@@ -44,8 +44,13 @@ enum RawKind : uint32_t {
     RAW_JARO = 2,  // Jaro flags + transpositions
     RAW_WF = 4,    // generalized-weights Levenshtein, Wagner-Fischer rows in LDS
     RAW_OSA = 3,   // optimal string alignment distance (Hyyro + transposition term)
-    RAW_DL = 5     // unrestricted Damerau-Levenshtein distance, row DP over packed cells (rf_damerau.hip)
+    RAW_DL = 5,    // unrestricted Damerau-Levenshtein distance, row DP over packed cells (rf_damerau.hip)
+    // the byte compares of rf_compare.hip: no recurrence, no pattern table -- the payload XOR the query at the same positions
+    RAW_HAMMING = 6,  // mismatches over the common length + the length difference
+    RAW_PREFIX = 7,   // length of the common prefix
+    RAW_POSTFIX = 8   // length of the common suffix
 };
+inline bool raw_is_compare(RawKind raw) { return raw == RAW_HAMMING || raw == RAW_PREFIX || raw == RAW_POSTFIX; }
 
 // how the raw per-candidate primitive becomes the reference's return value
 enum Finish : uint32_t {
@@ -107,6 +112,12 @@ struct ScanParams {
     uint32_t wf_waves;              // wavefronts per workgroup of wf_kernel (LDS rows per wavefront: (len1 + 1) * 256 B)
     uint32_t dl_reg;                // rf_damerau.hip: 1 = dl_reg_kernel (query <= 64 and max(len1, longest candidate) <= 254: wf_query holds the query), 0 = dl_kernel,
     uint32_t dl_wide;               // whose cells have 8-bit fields (0: nothing beyond 254 symbols) or 16-bit fields (1); rows in LDS or global by wf_waves / wf_global
+    // rf_compare.hip, hamming without RF_FLAG_HAMMING_PAD: a candidate whose length differs from the query's is the reference's Err(DifferentLengthArgs).  The decision
+    // is the tile's (one length per tile): such a tile is answered without reading its payload -- with RF_DIFFERENT_LENGTH_U32 / RF_DIFFERENT_LENGTH_F64_BITS where the
+    // caller's vector is per candidate (cmp_err_encode = 1: rf_many_*, rf_one_*, rf_many_multi_*, rf_stream_many_*), with the ordinary None everywhere else: whatever
+    // selects or compacts a result vector afterwards knows Some and None only
+    uint32_t cmp_strict;
+    uint32_t cmp_err_encode;
     uint32_t tile_step;             // >= 1: visit every tile_step-th tile of the range (the top-k bound sample)
     uint32_t head_need, head_k;     // head-plane cutoff scans: >= head_need of the first 8 symbols must have a partner within head_k positions (0 = filter off)
     // head_filter_kernel's product: the tiles a cutoff scan still has to walk ([0] = their number, then the tiles); tile_list_buf is
@@ -231,7 +242,7 @@ hipError_t launch_take_rows_len(const TakeParams& p, hipStream_t stream);  // id
 hipError_t launch_take_rows(const TakeParams& p, hipStream_t stream);      // row_slot, row_len, offsets -> out
 hipError_t launch_take_all(const TakeParams& p, hipStream_t stream);       // every candidate, walking tiles: offsets -> out
 
-// kernel launchers (rf_scan.hip, rf_long.hip, rf_damerau.hip, rf_jaro.hip, rf_pack.hip)
+// kernel launchers (rf_scan.hip, rf_long.hip, rf_damerau.hip, rf_compare.hip, rf_jaro.hip, rf_pack.hip)
 hipError_t launch_scan(RawKind raw, const ScanParams& p, hipStream_t stream, int* grid_used);
 hipError_t launch_osa1_asm(const ScanParams& p, hipStream_t stream, int grid);   // the same around the OSA column (OsaState<1>)
 hipError_t launch_lev32_asm(const ScanParams& p, hipStream_t stream, int grid);  // the same for queries of <= 32 symbols (Lev32State)
@@ -269,6 +280,7 @@ hipError_t launch_scan_mixed(RawKind raw, const ScanParams& p, hipStream_t strea
 hipError_t launch_long(RawKind raw, const ScanParams& p, hipStream_t stream, int grid);
 hipError_t launch_wf(const ScanParams& p, hipStream_t stream);
 hipError_t launch_dl(const ScanParams& p, hipStream_t stream);  // rf_damerau.hip
+hipError_t launch_compare(RawKind raw, const ScanParams& p, hipStream_t stream);  // rf_compare.hip: RAW_HAMMING / RAW_PREFIX / RAW_POSTFIX
 hipError_t launch_jaro(const ScanParams& p, hipStream_t stream);
 hipError_t launch_scan_multi(RawKind raw, bool narrow, const ScanParams& p, hipStream_t stream);
 hipError_t launch_topk_final(const uint64_t* keys, uint32_t count, uint32_t k, uint64_t* out, hipStream_t stream);

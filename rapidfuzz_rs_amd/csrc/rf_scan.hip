@@ -1314,6 +1314,9 @@ hipError_t launch_scan(RawKind raw, const ScanParams& p_in, hipStream_t stream, 
     case RAW_OSA: return launch_words<OsaState>(raw, p, stream, grid);
     case RAW_WF: return launch_wf(p, stream);
     case RAW_DL: return launch_dl(p, stream);
+    case RAW_HAMMING:
+    case RAW_PREFIX:
+    case RAW_POSTFIX: return launch_compare(raw, p, stream);
     case RAW_JARO: return launch_jaro(p, stream);
     default: return hipErrorInvalidValue;
     }

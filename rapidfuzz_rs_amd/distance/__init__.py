@@ -7,7 +7,10 @@ indel = _M("indel", _N.INDEL, False)                      # src/distance/indel.r
 lcs_seq = _M("lcs_seq", _N.LCS_SEQ, False)                # src/distance/lcs_seq.rs
 osa = _M("osa", _N.OSA, False)                            # src/distance/osa.rs
 damerau_levenshtein = _M("damerau_levenshtein", _N.DAMERAU_LEVENSHTEIN, False)  # src/distance/damerau_levenshtein.rs
+hamming = _M("hamming", _N.HAMMING, False)                # src/distance/hamming.rs (Args().pad(True): hamming.rs:112-118)
+prefix = _M("prefix", _N.PREFIX, False)                   # src/distance/prefix.rs
+postfix = _M("postfix", _N.POSTFIX, False)                # src/distance/postfix.rs
 jaro = _M("jaro", _N.JARO, True)                          # src/distance/jaro.rs
 jaro_winkler = _M("jaro_winkler", _N.JARO_WINKLER, True)  # src/distance/jaro_winkler.rs
 
-__all__ = ["levenshtein", "indel", "lcs_seq", "osa", "damerau_levenshtein", "jaro", "jaro_winkler"]
+__all__ = ["levenshtein", "indel", "lcs_seq", "osa", "damerau_levenshtein", "hamming", "prefix", "postfix", "jaro", "jaro_winkler"]
