@@ -434,6 +434,7 @@ rf_status rf_one_f64(const rf_comparator *c, const uint8_t *s2, size_t len2, rf_
  *   *out_count   (host) the number of candidates that passed -- ALWAYS the true number.  If it exceeds `capacity` the arrays hold `capacity` of the qualifying
  *                pairs (valid, in the requested order among themselves, not necessarily the first ones) and the caller repeats the call with room for
  *                *out_count: nothing is ever dropped silently.
+ *                A call that does not return RF_OK writes none of its outputs, the count included (this holds for rf_topk_*, rf_one_* and the *_multi calls too).
  *   order        RF_FILTER_BY_INDEX: ascending index.  RF_FILTER_BY_SCORE: best first (ascending for the distance ops, descending for the similarity ops),
  *                ties by ascending index.  RF_FILTER_ANY: whatever the scan produces (storage order of the packed corpus: cheapest for length-bucketed corpora).
  *   out_mem      where out_index / out_score live.  The call synchronizes `stream` either way (the count comes back to the host).

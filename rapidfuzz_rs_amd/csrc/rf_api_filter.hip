@@ -132,7 +132,7 @@ static rf_status run_filter(const rf_comparator* c, const rf_corpus* corpus, rf_
         set_error("rf_filter: null handle / args / count, null output with a non-zero capacity, or unknown order");
         return RF_ERR_INVALID_ARG;
     }
-    *out_count = 0;
+    // (the count is written by a call that returns RF_OK only: a refused call leaves every output as it was)
     if (corpus->n == 0) {  // argument errors of the scan itself (metric x op x output type) even when there is nothing to scan; otherwise the roads below report them
         ScanParams p;
         RawKind raw = RAW_LEV;
@@ -140,6 +140,7 @@ static rf_status run_filter(const rf_comparator* c, const rf_corpus* corpus, rf_
         ComparatorRef hold;
         if (resolve(c, corpus, &ce, &hold) == RF_OK)
             if (const rf_status rs = plan(ce, corpus, op, args, f64_out, &p, &raw); rs != RF_OK) return rs;
+        *out_count = 0;
         return RF_OK;
     }
     DeviceGuard guard(corpus->device);

@@ -219,9 +219,12 @@ try {
             return RF_ERR_INVALID_ARG;
         }
     }
+    const rf_args args_v = sanitized_args(args_in, false), *args = &args_v;
+    if (corpus->n != 0)  // what plan() refuses on every road is refused here, before a count is written
+        for (uint32_t i = 0; i < q; ++i)
+            if (const rf_status s = refused_by_plan(cs[i], corpus, op, args, false); s != RF_OK) return s;
     for (uint32_t i = 0; i < q; ++i) out_count[i] = 0;
     if (corpus->n == 0) return RF_OK;
-    const rf_args args_v = sanitized_args(args_in, false), *args = &args_v;
 
     FusedFilter fz;
     if (const rf_status s = filter_multi_fused(false, cs, q, corpus, op, args, capacity, (hipStream_t)stream, &fz); s != RF_OK) return s;
@@ -304,9 +307,12 @@ try {
         }
     }
     if (q == 0) return RF_OK;
+    const rf_args args_v = sanitized_args(args_in, false), *args = &args_v;
+    if (corpus->n != 0)  // what plan() refuses on every road is refused here, before a count is written
+        for (uint32_t i = 0; i < q; ++i)
+            if (const rf_status s = refused_by_plan(cs[i], corpus, op, args, true); s != RF_OK) return s;
     for (uint32_t i = 0; i < q; ++i) out_count[i] = 0;
     if (corpus->n == 0) return RF_OK;
-    const rf_args args_v = sanitized_args(args_in, false), *args = &args_v;
 
     FusedFilter fz;
     if (const rf_status s = filter_multi_fused(true, cs, q, corpus, op, args, capacity, (hipStream_t)stream, &fz); s != RF_OK) return s;

@@ -405,6 +405,19 @@ rf_status plan(const rf_comparator* c, const rf_corpus* corpus, rf_op op, const 
     return RF_OK;
 }
 
+// What plan() refuses for (c, corpus, op, args) on every road -- a query beyond what a kernel holds, weights or lengths beyond the u32 results -- asked before
+// anything runs: the multi-query entry points ask it for every query before they write a count, so that a refused call leaves its outputs as they were.
+// (A query that resolve() cannot lower is make_effective()'s, per call; argument errors are the entry points' own.)
+rf_status refused_by_plan(const rf_comparator* c, const rf_corpus* corpus, rf_op op, const rf_args* args, bool f64_out)
+{
+    const rf_comparator* ce = nullptr;
+    ComparatorRef hold;
+    if (resolve(c, corpus, &ce, &hold) != RF_OK) return RF_OK;
+    ScanParams p;
+    RawKind raw = RAW_LEV;
+    return plan(ce, corpus, op, args, f64_out, &p, &raw) == RF_ERR_UNSUPPORTED ? RF_ERR_UNSUPPORTED : RF_OK;
+}
+
 // bytes of per-launch scratch the planned kernels need (0 = none): carry strips of long_kernel, the global DP rows of
 // wf_kernel, the flag strips of jaro_long_kernel -- all handed to the kernels through ScanParams::long_scratch
 static size_t launch_scratch_bytes(const ScanParams& p, RawKind raw)
@@ -1387,16 +1400,20 @@ static rf_status run_one(const rf_comparator* c, const uint8_t* s2, size_t len2,
     rf_corpus* corpus = nullptr;
     rf_status s = rf_corpus_pack(s2, offsets, 1, device, &corpus);
     if (s != RF_OK) return s;
-    if (f64_out) {
+    if (f64_out) {  // (the value and the flag are written by a call that returns RF_OK only)
         double v = 0.0;
         s = run_many(c, corpus, op, args, &v, RF_MEM_HOST, nullptr, true);
-        *static_cast<double*>(out) = v;
-        *is_some = !std::isnan(v);
+        if (s == RF_OK) {
+            *static_cast<double*>(out) = v;
+            *is_some = !std::isnan(v);
+        }
     } else {
         uint32_t v = 0;
         s = run_many(c, corpus, op, args, &v, RF_MEM_HOST, nullptr, false);
-        *static_cast<uint32_t*>(out) = v;
-        *is_some = v != RF_NONE_U32;
+        if (s == RF_OK) {
+            *static_cast<uint32_t*>(out) = v;
+            *is_some = v != RF_NONE_U32;
+        }
     }
     rf_corpus_free(corpus);
     return s;

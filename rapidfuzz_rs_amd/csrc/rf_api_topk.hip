@@ -248,8 +248,10 @@ try {
         set_error("rf_topk_f64: invalid argument");
         return RF_ERR_INVALID_ARG;
     }
-    *out_count = 0;
-    if (corpus->n == 0 || k == 0) return RF_OK;
+    if (corpus->n == 0 || k == 0) {  // (the count is written by a call that returns RF_OK only)
+        *out_count = 0;
+        return RF_OK;
+    }
     DeviceGuard guard(corpus->device);
     if (!guard.ok) {
         set_error("cannot select the corpus' device");
@@ -279,12 +281,14 @@ try {
         set_error("rf_topk_u32: invalid argument");
         return RF_ERR_INVALID_ARG;
     }
-    *out_count = 0;
     if (k == 0) {
         set_error("top-k: k must be at least 1");
         return RF_ERR_INVALID_ARG;
     }
-    if (corpus->n == 0) return RF_OK;
+    if (corpus->n == 0) {  // (the count is written by a call that returns RF_OK only)
+        *out_count = 0;
+        return RF_OK;
+    }
     if (k > (uint32_t)kWave) {
         // more than one list entry per wavefront lane: the selection path (any k; also general weight tables, long queries)
         if (op != RF_OP_DISTANCE && op != RF_OP_SIMILARITY) {

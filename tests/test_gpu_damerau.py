@@ -1,6 +1,7 @@
 """damerau_levenshtein::BatchComparator on the device (rf_damerau.hip), bit-exact against tests/dl_reference.py: the reference's known answers,
 parity over corpus shapes x query lengths x ops x cutoffs (the register kernels, the LDS rows with 8- and 16-bit fields, the global rows), every
-result road, two pack-time layouts through child processes, and a randomized differential test.
+result road, two pack-time layouts through child processes, a randomized differential test, the steps of the plan from the query's side (149 / 150, 254 / 255, and with
+a 255-symbol candidate 74 / 75, 99 / 100, 149 / 150, 299 / 300) and the field limit (65 534 symbols answered on either side, 65 535 refused with the output untouched).
 Here every wavefront walks ONE tile; several tiles per wavefront of each of these kernels: tests/multitile_rowdp_check.py, mode "damerau" (started by tests/test_gpu_parity.py).
 
 The inputs are chosen so that a kernel computing a NEIGHBOURING metric fails: near-duplicates are planted by "swap two adjacent symbols and insert
@@ -192,6 +193,135 @@ def test_chars_corpus_parity():
     # a query symbol the corpus does not hold never matches
     q2 = q[:10] + [0x4E2D] + q[10:]
     _eq(DL.BatchComparator("".join(map(chr, q2))).distance_many(corpus), R.ops(N.OP_DISTANCE, q2, rows, lens), "chars, absent symbol")
+
+
+# ------------------------------------------------------------------------------------------------ the query-side edges of the plan
+# (query length, a 255-symbol candidate inserted, the plan): plan() (rf_api_scan.hip) picks the cell width from the longest string of the call -- 8-bit fields up
+# to 254 symbols, 16-bit from 255 on -- and the wavefronts per workgroup from the row of len1 x 64 cells (4 bytes narrow, 8 wide) within 150 KiB of LDS less
+# len1 + 16: waves = min(4, (153600 - len1 - 16) // row_bytes), the global strip when not even one row fits.
+#   narrow  149: 153435 // 38144 = 4    150: 153434 // 38400 = 3    254: 153330 // 65024 = 2
+#   wide     74: 153510 // 37888 = 4     75: 153509 // 38400 = 3     99: 153485 // 50688 = 3    100: 153484 // 51200 = 2    149: 153435 // 76288 = 2
+#           150: 153434 // 76800 = 1    255: 153329 // 130560 = 1   299: 153088 + 299 + 16 = 153403 <= 153600, one row    300: 153600 + 316 > 153600: global
+DL_EDGE_LEGS = [(149, False, "lds8 x4"), (150, False, "lds8 x3"), (254, False, "lds8 x2"), (255, False, "lds16 x1"),
+                (74, True, "lds16 x4"), (75, True, "lds16 x3"), (99, True, "lds16 x3"), (100, True, "lds16 x2"), (149, True, "lds16 x2"), (150, True, "lds16 x1"),
+                (299, True, "lds16 x1"), (300, True, "global16")]
+
+
+def _dl_plan(len1, longest):
+    """the plan of a damerau_levenshtein launch, with the arithmetic of tests/multitile_rowdp_check.py dl_waves"""
+    import multitile_rowdp_check as M
+
+    wide = max(len1, longest) > 254
+    if not wide and len1 <= 64:
+        return "reg"
+    cells = 16 if wide else 8
+    if max(len1, 1) * 64 * (8 if wide else 4) + len1 + 16 > M.LDS_BUDGET:
+        return f"global{cells}"
+    return f"lds{cells} x{M.dl_waves(len1, longest)}"
+
+
+@pytest.mark.parametrize("qlen,wide_candidate,plan", DL_EDGE_LEGS)
+def test_query_side_edges_of_the_plan(qlen, wide_candidate, plan):
+    """about 200 candidates of up to 64 symbols and 60 planted near-duplicates, one ragged corpus law for every leg; with `wide_candidate` one 255-symbol
+    candidate among them makes the cells wide"""
+    rng = np.random.default_rng(4242)
+    sym = 62
+    cands = [_rand(rng, int(rng.integers(0, 65)), sym) for _ in range(200)]
+    q = _rand(np.random.default_rng(qlen), qlen, sym)
+    plant = [_planted(rng, q[:60], sym) for _ in range(60)]  # (planted in the query's first 60 symbols: the clip to 64 leaves every swap in)
+    assert _frac_below_osa(q, plant[:12]) >= 0.5  # the inputs: the planted rows tell this metric from OSA
+    cands = [(cands + plant)[i] for i in rng.permutation(len(cands) + len(plant))]
+    dist = R.dl_many(q, *R.pad_rows(cands))
+    if wide_candidate:
+        long_one = (_planted(rng, q, sym, clip=255) + _rand(rng, 255, sym))[:255]
+        cands.insert(77, long_one)
+        dist = np.insert(dist, 77, R.dl_pair(q, long_one))  # (the vectorised form walks every column of the longest row: the per-pair form for this one)
+    longest = max(len(c) for c in cands)
+    assert longest == (255 if wide_candidate else 64) and _dl_plan(qlen, longest) == plan  # the inputs: this leg is the plan it says
+    corpus, rows, lens = _bytes_corpus(cands)
+    bc = DL.BatchComparator(bytes(48 + v for v in q))
+    qv = [48 + v for v in q]
+    for op in OPS:
+        _eq(bc.many(op, corpus), R.ops(op, qv, rows, lens, None, dist), f"query {qlen} ({plan}) op {op}")
+        for c in _cutoffs(op, qlen, lens):
+            _eq(bc.many(op, corpus, score_cutoff=c), R.ops(op, qv, rows, lens, c, dist), f"query {qlen} ({plan}) op {op} cutoff {c}")
+
+
+def test_the_plans_of_the_query_side_edges_change_where_they_say():
+    """host arithmetic only: each pair of neighbouring lengths sits on either side of a step of the plan"""
+    plans = {(q, w): p for q, w, p in DL_EDGE_LEGS}
+    for lo, hi, w in ((149, 150, False), (254, 255, False), (74, 75, True), (99, 100, True), (149, 150, True), (299, 300, True)):
+        assert plans[(lo, w)] != plans[(hi, w)], (lo, hi, w)
+        assert _dl_plan(lo, 255 if w else 64) == plans[(lo, w)] and _dl_plan(hi, 255 if w else 64) == plans[(hi, w)]
+    assert {p for (_, w), p in plans.items() if w} == {"lds16 x4", "lds16 x3", "lds16 x2", "lds16 x1", "global16"}
+
+
+# ------------------------------------------------------------------------------------------------ the field limit: 65 534 symbols accepted, 65 535 refused
+FIELD_MAX = 65_534  # the largest length the 16-bit fields of a cell hold (rf_dl_cell.hpp); 65 535 is their "infinity"
+
+
+def _limit_parity(q, cands, what):
+    dist = np.array([R.dl_pair(q, c) for c in cands], dtype=np.int64)  # (per pair: a few hundred thousand cells each)
+    corpus, rows, lens = _bytes_corpus(cands, base=0)
+    bc = DL.BatchComparator(bytes(q))
+    for op in OPS:
+        _eq(bc.many(op, corpus), R.ops(op, q, rows, lens, None, dist), f"{what} op {op}")
+    for op, c in ((N.OP_DISTANCE, FIELD_MAX), (N.OP_DISTANCE, FIELD_MAX - 1), (N.OP_DISTANCE, int(dist.min())), (N.OP_SIMILARITY, 1), (N.OP_SIMILARITY, 0),
+                  (N.OP_NORMALIZED_DISTANCE, 1.0), (N.OP_NORMALIZED_SIMILARITY, 1e-4)):
+        _eq(bc.many(op, corpus, score_cutoff=c), R.ops(op, q, rows, lens, c, dist), f"{what} op {op} cutoff {c}")
+    return dist
+
+
+def test_a_query_of_65534_symbols():
+    rng = np.random.default_rng(65534)
+    q = [int(v) for v in rng.integers(1, 5, size=FIELD_MAX)]
+    cands = [[], q[100:108], [q[201], q[200], 9, q[203]]]  # nothing, a piece of the query, a piece with a swap and a symbol the query does not hold
+    assert len(q) == FIELD_MAX and max(len(c) for c in cands) <= 8
+    dist = _limit_parity(q, cands, "query of 65534")
+    assert int(dist.max()) == FIELD_MAX and len(set(dist.tolist())) >= 3  # the largest value a field can hold is a result
+
+
+def test_candidates_of_65534_and_65533_symbols():
+    rng = np.random.default_rng(65533)
+    q = [1, 2, 3]
+    cands = [[9] * FIELD_MAX, [int(v) for v in rng.integers(1, 5, size=FIELD_MAX - 1)], [int(v) for v in rng.integers(1, 5, size=40)]]
+    assert [len(c) for c in cands] == [FIELD_MAX, FIELD_MAX - 1, 40]
+    dist = _limit_parity(q, cands, "candidates of 65534")
+    assert int(dist[0]) == FIELD_MAX and len(set(dist.tolist())) >= 3
+
+
+@pytest.mark.parametrize("side", ["query", "candidate"])
+def test_a_string_of_65535_symbols_is_refused_with_the_output_untouched(side):
+    import ctypes as C
+
+    rng = np.random.default_rng(65535)
+    long_one = bytes(int(v) for v in rng.integers(1, 5, size=FIELD_MAX + 1))
+    short = [bytes(int(v) for v in rng.integers(1, 5, size=int(rng.integers(0, 9)))) for _ in range(70)]
+    q, cands = (long_one, short) if side == "query" else (bytes([1, 2, 3]), short[:30] + [long_one] + short[30:])
+    assert max(len(q), max(len(c) for c in cands)) == FIELD_MAX + 1
+    corpus = rf.Corpus.from_list(cands)
+    bc = DL.BatchComparator(q)
+    a = N.RfArgs()
+    N.lib().rf_args_default(C.byref(a))
+    out = np.full(len(cands), 0xA5A5A5A5, dtype=np.uint32)
+    assert N.lib().rf_many_u32(bc._h, corpus._h, N.OP_DISTANCE, C.byref(a), out.ctypes.data, N.MEM_HOST, None) == N.RF_ERR_UNSUPPORTED
+    assert "65535" in N.lib().rf_last_error().decode() and (out == 0xA5A5A5A5).all()
+    outf = np.full(len(cands), 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)
+    assert N.lib().rf_many_f64(bc._h, corpus._h, N.OP_NORMALIZED_SIMILARITY, C.byref(a), outf.ctypes.data, N.MEM_HOST, None) == N.RF_ERR_UNSUPPORTED
+    assert (outf == 0xA5A5A5A5A5A5A5A5).all()
+    for call in (lambda: bc.distance_many(corpus), lambda: bc.topk(corpus, 5), lambda: bc.filter_many(N.OP_DISTANCE, corpus, score_cutoff=3)):
+        with pytest.raises(N.RfError) as e:
+            call()
+        assert e.value.status == N.RF_ERR_UNSUPPORTED
+    # one symbol fewer on that side is answered
+    if side == "query":
+        q = q[:-1]
+    else:
+        cands[30] = cands[30][:-1]
+        corpus = rf.Corpus.from_list(cands)
+    got = DL.BatchComparator(q).distance_many(corpus)
+    i = 5 if side == "query" else 30
+    assert int(got[i]) == R.dl_pair(list(q), list(cands[i]))
 
 
 # ------------------------------------------------------------------------------------------------ every road
