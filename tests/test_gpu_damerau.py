@@ -86,6 +86,45 @@ def _parity(q_bytes, corpus, rows, lens, what, ops=OPS, cutoffs=True):
     return dist
 
 
+def test_normalized_cutoffs_that_equal_a_produced_quotient():
+    """f64 cutoffs that ARE a candidate's d / maximum (or 1 - d / maximum) and the doubles on either side of it: 200 candidates of 0..40 symbols, a query of 24,
+    at most 12 of the produced values by rank (the smallest and the largest among them), against tests/dl_reference.py called WITH the cutoff -- every value
+    bit-equal, every None a None -- through many, filter_many and top-k.  The round decimals of _cutoffs() almost never equal a score, so they cannot tell
+    `<=` from `<` in emit_fin's compare."""
+    rng = np.random.default_rng(2406)
+    q = _rand(rng, 24, 12)
+    cands = [_planted(rng, q, 12) if i % 4 == 0 else _rand(rng, int(rng.integers(0, 41)), 12) for i in range(200)]
+    cands[4] = list(q)
+    corpus, rows, lens = _bytes_corpus(cands)
+    qb = bytes(48 + v for v in q)
+    qv = list(qb)
+    bc = DL.BatchComparator(qb)
+    dist = R.dl_many(qv, rows, lens)
+    told_apart = 0
+    for op in (N.OP_NORMALIZED_DISTANCE, N.OP_NORMALIZED_SIMILARITY):
+        full = R.ops(op, qv, rows, lens, None, dist)
+        vals = np.unique(full)
+        picked = vals[np.unique(np.linspace(0, len(vals) - 1, num=12).round().astype(int))]
+        assert len(picked) >= 8 and picked[0] == vals[0] and picked[-1] == vals[-1] and 0.0 in vals.tolist() + (1.0 - vals).tolist()
+        for v in picked:
+            triple = [float(np.nextafter(v, -1.0)), float(v), float(np.nextafter(v, 2.0))]
+            kept = []
+            for c in triple:
+                exp = R.ops(op, qv, rows, lens, c, dist)
+                kept.append(int(np.count_nonzero(~np.isnan(exp))))
+                got = bc.many(op, corpus, score_cutoff=c)
+                same = (np.isnan(got) & np.isnan(exp)) | (got.view(np.uint64) == exp.view(np.uint64))
+                assert same.all(), (op, c, np.nonzero(~same)[0][:5], got[~same][:5], exp[~same][:5])
+                some = np.nonzero(~np.isnan(exp))[0]
+                idx, sc = bc.filter_many(op, corpus, score_cutoff=c)
+                assert idx.tolist() == some.tolist() and sc.view(np.uint64).tolist() == exp[some].view(np.uint64).tolist(), (op, c)
+                best = some[np.lexsort((some, exp[some] if op == N.OP_NORMALIZED_DISTANCE else -exp[some]))][:16]
+                scores, at = bc.topk(corpus, 16, op=op, score_cutoff=c)
+                assert at.tolist() == best.tolist() and scores.view(np.uint64).tolist() == exp[best].view(np.uint64).tolist(), (op, c)
+            told_apart += kept[0] != kept[2]
+    assert told_apart >= 16  # (the neighbours of a produced value keep different numbers of candidates: a flipped compare shows)
+
+
 # ------------------------------------------------------------------------------------------------ known answers
 def test_known_answers_through_one_and_through_a_corpus():
     for a, b, d in KNOWN:
