@@ -9,19 +9,60 @@
 
 extern "C" {
 
-constexpr size_t kHeadPlaneWins = size_t(1) << 25;  // candidates of a single-length corpus from which small-cutoff Levenshtein queries go per query (see the planner below)
-constexpr size_t kHeadPlaneWinsF64 = size_t(3) << 23;  // the same for the f64 plans of rf_filter_multi_f64 (25.2 M: see the planner below)
+constexpr size_t kHeadPlaneWins = size_t(1) << 25;  // candidates of a single-length corpus from which small-cutoff Levenshtein queries go per query (see head_plane_wins below)
+constexpr size_t kHeadPlaneWinsF64 = size_t(3) << 23;  // the same for the f64 plans of rf_filter_multi_f64 (25.2 M: see head_plane_wins below)
 // A/B switch: 0 sends every query down the per-query road (identical results)
 static bool sw_filter_multi() { static const bool v = env_on("RF_FILTER_MULTI"); return v; }
 // A/B switch of the f64 planner: 0 fuses every fusable query of rf_filter_multi_f64, also the shapes its measured routing rules send per query
 static bool sw_filter_multi_f64_route() { static const bool v = env_on("RF_FILTER_MULTI_F64_ROUTE"); return v; }
 
-// What rf_filter_multi_u32 and rf_filter_multi_f64 share, after their argument checks: plan every query, group the fusable ones, run the groups and bring
-// their counters and key rows home.  `norm` (rf_filter_multi_f64): f64-valued plans, the normalized kernels, and one more condition on a fusable query -- the
-// largest maximum it can meet in this corpus fits the 32-bit score image (rf_topk_multi_f64's rule).
+// The one shape the fused road lost (tools/bench_filter_multi.py, profiles/filter_multi.txt): Levenshtein under a small cutoff over a LARGE single-length
+// corpus, where rf_filter_u32 takes its first look from the 8-byte head plane and compacts lanes (6-8 B per pair, 8 columns) while a fused group reads
+// the payload's 16-byte first chunk: 100 M x 64, cutoff 3, 16 / 256 queries 5.67 / 89.5 ms fused against 3.00 / 53.7 ms per query; at 10 M the fused
+// road still wins (0.92 / 14.1 against 1.64 / 23.9 ms).  Between the two sizes the boundary is interpolated from those four times (fixed cost + slope of
+// either road: about 2^25 candidates for a group of four); the one size measured beside it, 30 M, is level at 16 queries and 1.10 x at 256
+// (profiles/filter_multi_copy.txt).  A query whose length window is empty stays fused: it launches nothing.
+// The f64 plans (tools/bench_filter_multi_f64.py, profiles/filter_multi_f64.txt; 16 / 256 queries of 64 symbols): rf_filter_f64 takes the same head-plane road
+// for such a query -- first_check <= 8 is normalized_similarity >= 0.95 over 64-symbol candidates, and RF_TRACE_PLAN shows heads8=1 for its scans -- and the
+// fused road, which also pays an f64 division per look, falls behind EARLIER.  normalized_similarity >= 0.95, fused (RF_FILTER_MULTI_F64_ROUTE=0) against the loop: 20 M
+// 1.39 / 20.4 ms against 1.93 / 27.0 (1.39 / 1.33 x), 24 M 1.65 / 24.2 against 1.72 / 30.6 (1.04 / 1.27 x; second run 1.12 / 1.13 x), 30 M 2.02 / 30.0 against
+// 1.98 / 32.5 (0.98 / 1.08 x; first session 0.96 / 1.03 x: at 16 queries the fused road LOSES), 100 M 6.24 / 96.9 against 3.02 / 49.7 (0.48 / 0.51 x).  So the
+// boundary sits between the last size where both query counts win by more than the spread, 24 M, and the first where one loses, 30 M: 3 x 2^23 = 25.2 M.
+// A cutoff whose first look comes later (normalized_similarity >= 0.9: first_check 10, no head plane per query) stays fused at every size: 100 M 8.58 / 135.9 ms
+// against 11.01 / 172.2 (1.28 / 1.27 x).
+static bool head_plane_wins(const ScanParams& p, RawKind raw, const rf_corpus* corpus, bool norm)
+{
+    return raw == RAW_LEV && corpus->uniform && corpus->n >= (norm ? kHeadPlaneWinsF64 : kHeadPlaneWins) && p.first_check <= 8 && p.tile_begin < p.tile_end && (!norm || sw_filter_multi_f64_route());
+}
+
+// ... and the argument checks of the two: everything is decided before the corpus is looked at or a device is touched, and before anything is written
+static rf_status check_filter_multi_args(const char* fn, bool f64, const rf_comparator* const* cs, uint32_t q, const rf_corpus* corpus, rf_op op, const rf_args* args_in,
+                                         uint64_t capacity, const uint64_t* out_index, const void* out_score, const uint64_t* out_count, rf_filter_order order, rf_args* args)
+{
+    const std::string name(fn);
+    if (!cs || !corpus || !args_in || !out_count) {
+        set_error(name + ": null handle, args or count");
+        return RF_ERR_INVALID_ARG;
+    }
+    if (capacity && (!out_index || !out_score)) {
+        set_error(name + ": null output with a non-zero capacity");
+        return RF_ERR_INVALID_ARG;
+    }
+    if ((int)order < 0 || (int)order > (int)RF_FILTER_ANY) {
+        set_error(name + ": unknown order");
+        return RF_ERR_INVALID_ARG;
+    }
+    const std::string usize_only = name + ": usize-valued metrics only (jaro / jaro_winkler / fuzz ratio: rf_filter_f64)";
+    if (const rf_status s = check_multi_members(fn, f64, usize_only.c_str(), cs, q, op); s != RF_OK) return s;
+    *args = sanitized_args(args_in, false);
+    return RF_OK;
+}
+
+// What rf_filter_multi_u32 and rf_filter_multi_f64 share, after their argument checks: plan every query (a refusal comes before a count is written), run the fused
+// groups and bring their counters and key rows home.  `norm` (rf_filter_multi_f64): f64-valued plans and the normalized kernels.  Fused: plans under a tight cutoff
+// (`early`), but for the shapes head_plane_wins() sends per query.
 struct FusedFilter {
-    std::vector<std::vector<uint32_t>> groups;  // members of each fused group, as indices into cs
-    std::vector<char> taken;                    // [q] 1: the query is in a group
+    MultiPlan plan;
     uint32_t seg_cap = 0;                       // keys a row can hold: min(capacity, n)
     // the results at home.  Row r = the r-th fused member in group order: count(r) is its true number of matches, keys(r) its first min(count, seg_cap) keys in
     // the order of arrival -- (score, ~score or norm_key) << 32 | local index
@@ -33,72 +74,17 @@ struct FusedFilter {
     uint64_t* keys(uint32_t r) { return one_copy ? reinterpret_cast<uint64_t*>(home.data() + ctl_bytes) + (size_t)r * seg_cap : big.data() + (size_t)r * width; }
 };
 static rf_status filter_multi_fused(bool norm, const rf_comparator* const* cs, uint32_t q, const rf_corpus* corpus, rf_op op, const rf_args* args, uint64_t capacity,
-                                    hipStream_t st, FusedFilter* out)
+                                    uint64_t* out_count, hipStream_t st, FusedFilter* out)
 {
-    // ---- plan every query; which ones can be fused
-    std::vector<ScanParams> ps(q);
-    std::vector<RawKind> raws(q, RAW_LEV);
-    std::vector<const rf_comparator*> eff(q, nullptr);
-    std::vector<ComparatorRef> holds(q);
-    std::vector<char> fusable(q, 0);
-    if (sw_filter_multi())
-        for (uint32_t i = 0; i < q; ++i) {
-            // (a query that does not resolve -- overflow-class symbols need a translated image of the corpus -- or does not plan goes to
-            // the single-query call, which serves it or reports why not)
-            if (resolve(cs[i], corpus, &eff[i], &holds[i]) != RF_OK) continue;
-            if (plan(eff[i], corpus, op, args, norm, &ps[i], &raws[i]) != RF_OK) continue;
-            fusable[i] = (raws[i] == RAW_LEV || raws[i] == RAW_LCS) && eff[i]->words == 1 && !ps[i].long_words_pad && ps[i].early;
-            if (norm && fusable[i]) {
-                // the 32-bit score image (rf_norm_key.hpp) is exact while every maximum of the scan is <= 65535; the maximum grows with the candidate's length
-                const uint64_t len1 = ps[i].len1, len2 = corpus->max_len;
-                const uint64_t largest = (uint64_t)ps[i].fin_mS * (len1 + len2) + (uint64_t)ps[i].fin_mM * std::max(len1, len2);
-                fusable[i] = largest <= kNormKeyMaxMaximum;
-            }
-            // The one shape the fused road lost (tools/bench_filter_multi.py, profiles/filter_multi.txt): Levenshtein under a small cutoff over a LARGE single-length
-            // corpus, where rf_filter_u32 takes its first look from the 8-byte head plane and compacts lanes (6-8 B per pair, 8 columns) while a fused group reads
-            // the payload's 16-byte first chunk: 100 M x 64, cutoff 3, 16 / 256 queries 5.67 / 89.5 ms fused against 3.00 / 53.7 ms per query; at 10 M the fused
-            // road still wins (0.92 / 14.1 against 1.64 / 23.9 ms).  Between the two sizes the boundary is interpolated from those four times (fixed cost + slope of
-            // either road: about 2^25 candidates for a group of four); the one size measured beside it, 30 M, is level at 16 queries and 1.10 x at 256
-            // (profiles/filter_multi_copy.txt).  A query whose length window is empty stays fused: it launches nothing.
-            // The f64 plans (tools/bench_filter_multi_f64.py, profiles/filter_multi_f64.txt; 16 / 256 queries of 64 symbols): rf_filter_f64 takes the same head-plane road
-            // for such a query -- first_check <= 8 is normalized_similarity >= 0.95 over 64-symbol candidates, and RF_TRACE_PLAN shows heads8=1 for its scans -- and the
-            // fused road, which also pays an f64 division per look, falls behind EARLIER.  normalized_similarity >= 0.95, fused (RF_FILTER_MULTI_F64_ROUTE=0) against the loop: 20 M
-            // 1.39 / 20.4 ms against 1.93 / 27.0 (1.39 / 1.33 x), 24 M 1.65 / 24.2 against 1.72 / 30.6 (1.04 / 1.27 x; second run 1.12 / 1.13 x), 30 M 2.02 / 30.0 against
-            // 1.98 / 32.5 (0.98 / 1.08 x; first session 0.96 / 1.03 x: at 16 queries the fused road LOSES), 100 M 6.24 / 96.9 against 3.02 / 49.7 (0.48 / 0.51 x).  So the
-            // boundary sits between the last size where both query counts win by more than the spread, 24 M, and the first where one loses, 30 M: 3 x 2^23 = 25.2 M.
-            // A cutoff whose first look comes later (normalized_similarity >= 0.9: first_check 10, no head plane per query) stays fused at every size: 100 M 8.58 / 135.9 ms
-            // against 11.01 / 172.2 (1.28 / 1.27 x).
-            const size_t head_plane_wins = norm ? kHeadPlaneWinsF64 : kHeadPlaneWins;
-            if (fusable[i] && raws[i] == RAW_LEV && corpus->uniform && corpus->n >= head_plane_wins && ps[i].first_check <= 8 && ps[i].tile_begin < ps[i].tile_end &&
-                (!norm || sw_filter_multi_f64_route()))
-                fusable[i] = 0;
-        }
-    // (ps[].op: what the kernel computes -- a fuzz ratio plans to RF_OP_NORMALIZED_SIMILARITY whichever similarity op was asked for)
-    auto same_group = [&](uint32_t a, uint32_t b) {
-        return raws[a] == raws[b] && ps[a].finish == ps[b].finish && ps[a].factor == ps[b].factor && ps[a].op == ps[b].op &&
-               (ps[a].len1 <= 32) == (ps[b].len1 <= 32);
-    };
-    // (rows are independent, so a group's members need not be neighbours)
-    std::vector<std::vector<uint32_t>>& groups = out->groups;
-    std::vector<char>& taken = out->taken;
-    taken.assign(q, 0);
-    for (uint32_t i = 0; i < q; ++i) {
-        if (taken[i] || !fusable[i]) continue;
-        std::vector<uint32_t> g{i};
-        for (uint32_t j = i + 1; j < q && g.size() < (size_t)kMaxMulti; ++j)
-            if (!taken[j] && fusable[j] && same_group(i, j)) g.push_back(j);
-        if (g.size() == 3) g.pop_back();
-        if (g.size() < 2) continue;  // the odd one left over
-        for (uint32_t m : g) taken[m] = 1;
-        groups.push_back(std::move(g));
-    }
-    uint32_t fused = 0;
-    for (const auto& g : groups) fused += (uint32_t)g.size();
-    if (sw_trace_plan()) {
-        std::string sizes;
-        for (const auto& g : groups) sizes += (sizes.empty() ? "" : ",") + std::to_string(g.size());
-        std::fprintf(stderr, "[rf plan] %s: q=%u fused_groups=[%s] per_query=%u\n", norm ? "filter_multi_f64" : "filter_multi", q, sizes.c_str(), q - fused);
-    }
+    MultiPlan& mp = out->plan;
+    if (corpus->n != 0)
+        if (const rf_status s = plan_multi(MultiAsk{norm, true, sw_filter_multi(), head_plane_wins}, cs, q, corpus, op, args, &mp); s != RF_OK) return s;
+    for (uint32_t i = 0; i < q; ++i) out_count[i] = 0;
+    if (corpus->n == 0) return RF_OK;
+    const std::vector<ScanParams>& ps = mp.ps;
+    const std::vector<std::vector<uint32_t>>& groups = mp.g.groups;
+    const uint32_t fused = mp.fused;
+    mp.trace(norm ? "filter_multi_f64" : "filter_multi", "", "");
 
     // ---- the fused groups: everything enqueued, then the results home
     const uint32_t seg_cap = out->seg_cap = (uint32_t)std::min<uint64_t>(capacity, corpus->n);
@@ -136,14 +122,14 @@ static rf_status filter_multi_fused(bool norm, const rf_comparator* const* cs, u
                 const ScanParams& pm = ps[g[m]];
                 p.multi_len1[m] = pm.len1;
                 if (pm.tile_begin < pm.tile_end) t0 = std::min(t0, pm.tile_begin), t1 = std::max(t1, std::min(pm.tile_end, corpus->n_tiles));
-                status = comparator_device_pm(eff[g[m]], corpus->device, &p.multi_pm[m]);
+                status = comparator_device_pm(mp.eff[g[m]], corpus->device, &p.multi_pm[m]);
             }
             if (status != RF_OK) break;
             p.tile_begin = t0, p.tile_end = std::max(t0, t1);
             fp.count = d_count + (size_t)row * kFilterMultiLine32;
             fp.cand = seg_cap ? d_cand + (size_t)row * seg_cap : nullptr;
             fp.seg_cap = seg_cap;
-            e = launch_filter_multi(raws[i], p.len1 <= 32, fp, st);
+            e = launch_filter_multi(mp.raws[i], p.len1 <= 32, fp, st);
             row += (uint32_t)g.size();
         }
         std::vector<uint8_t>& home = out->home;
@@ -191,48 +177,18 @@ static rf_status filter_multi_fused(bool norm, const rf_comparator* const* cs, u
 rf_status rf_filter_multi_u32(const rf_comparator* const* cs, uint32_t q, const rf_corpus* corpus, rf_op op, const rf_args* args_in, uint64_t index_base,
                               uint64_t capacity, uint64_t* out_index, uint32_t* out_score, uint64_t* out_count, rf_filter_order order, void* stream)
 try {
-    // ---- arguments: everything here is decided before the corpus is looked at or a device is touched, and before anything is written
-    if (!cs || !corpus || !args_in || !out_count) {
-        set_error("rf_filter_multi_u32: null handle, args or count");
-        return RF_ERR_INVALID_ARG;
-    }
-    if (capacity && (!out_index || !out_score)) {
-        set_error("rf_filter_multi_u32: null output with a non-zero capacity");
-        return RF_ERR_INVALID_ARG;
-    }
-    if ((int)order < 0 || (int)order > (int)RF_FILTER_ANY) {
-        set_error("rf_filter_multi_u32: unknown order");
-        return RF_ERR_INVALID_ARG;
-    }
-    if (op != RF_OP_DISTANCE && op != RF_OP_SIMILARITY) {
-        set_error("rf_filter_multi_u32: op must be RF_OP_DISTANCE or RF_OP_SIMILARITY");
-        return RF_ERR_INVALID_ARG;
-    }
+    rf_args args_v;
+    const rf_args* args = &args_v;
+    if (const rf_status s = check_filter_multi_args("rf_filter_multi_u32", false, cs, q, corpus, op, args_in, capacity, out_index, out_score, out_count, order, &args_v); s != RF_OK) return s;
     if (q == 0) return RF_OK;
-    for (uint32_t i = 0; i < q; ++i) {
-        if (!cs[i]) {
-            set_error("rf_filter_multi_u32: null comparator");
-            return RF_ERR_INVALID_ARG;
-        }
-        if (cs[i]->metric == RF_JARO || cs[i]->metric == RF_JARO_WINKLER || cs[i]->metric == RF_FUZZ_RATIO) {
-            set_error("rf_filter_multi_u32: usize-valued metrics only (jaro / jaro_winkler / fuzz ratio: rf_filter_f64)");
-            return RF_ERR_INVALID_ARG;
-        }
-    }
-    const rf_args args_v = sanitized_args(args_in, false), *args = &args_v;
-    if (corpus->n != 0)  // what plan() refuses on every road is refused here, before a count is written
-        for (uint32_t i = 0; i < q; ++i)
-            if (const rf_status s = refused_by_plan(cs[i], corpus, op, args, false); s != RF_OK) return s;
-    for (uint32_t i = 0; i < q; ++i) out_count[i] = 0;
-    if (corpus->n == 0) return RF_OK;
-
     FusedFilter fz;
-    if (const rf_status s = filter_multi_fused(false, cs, q, corpus, op, args, capacity, (hipStream_t)stream, &fz); s != RF_OK) return s;
+    if (const rf_status s = filter_multi_fused(false, cs, q, corpus, op, args, capacity, out_count, (hipStream_t)stream, &fz); s != RF_OK) return s;
+    if (corpus->n == 0) return RF_OK;
     // order and decode as rf_filter_u32 does: by index ascending, or best score first with ties by index (a plain sort of the keys)
     {
         const bool desc = op == RF_OP_SIMILARITY;
         uint32_t row = 0;
-        for (const auto& g : fz.groups)
+        for (const auto& g : fz.plan.g.groups)
             for (uint32_t j : g) {
                 const uint32_t r = row++;
                 const uint32_t count = fz.count(r), have = std::min(count, fz.seg_cap);
@@ -252,7 +208,7 @@ try {
 
     // ---- everything else: the single-query filter, one call per query
     for (uint32_t j = 0; j < q; ++j) {
-        if (fz.taken[j]) continue;
+        if (fz.plan.g.taken[j]) continue;
         const rf_status s = rf_filter_u32(cs[j], corpus, op, args, index_base, capacity, capacity ? out_index + (size_t)j * capacity : nullptr,
                                           capacity ? out_score + (size_t)j * capacity : nullptr, out_count + j, RF_MEM_HOST, order, stream);
         if (s != RF_OK) return s;
@@ -270,55 +226,16 @@ RF_ABI_CATCH
 rf_status rf_filter_multi_f64(const rf_comparator* const* cs, uint32_t q, const rf_corpus* corpus, rf_op op, const rf_args* args_in, uint64_t index_base,
                               uint64_t capacity, uint64_t* out_index, double* out_score, uint64_t* out_count, rf_filter_order order, void* stream)
 try {
-    // ---- arguments: everything here is decided before the corpus is looked at or a device is touched, and before anything is written
-    if (!cs || !corpus || !args_in || !out_count) {
-        set_error("rf_filter_multi_f64: null handle, args or count");
-        return RF_ERR_INVALID_ARG;
-    }
-    if (capacity && (!out_index || !out_score)) {
-        set_error("rf_filter_multi_f64: null output with a non-zero capacity");
-        return RF_ERR_INVALID_ARG;
-    }
-    if ((int)order < 0 || (int)order > (int)RF_FILTER_ANY) {
-        set_error("rf_filter_multi_f64: unknown order");
-        return RF_ERR_INVALID_ARG;
-    }
-    if ((int)op < 0 || (int)op > (int)RF_OP_NORMALIZED_SIMILARITY) {
-        set_error("unknown rf_op");
-        return RF_ERR_INVALID_ARG;
-    }
-    const bool norm_op = op == RF_OP_NORMALIZED_DISTANCE || op == RF_OP_NORMALIZED_SIMILARITY;
-    // (a null or unacceptable comparator anywhere in the list is an error whatever q's other members are; q == 0 has none)
-    for (uint32_t i = 0; i < q; ++i) {
-        if (!cs[i]) {
-            set_error("rf_filter_multi_f64: null comparator");
-            return RF_ERR_INVALID_ARG;
-        }
-        const rf_metric m = cs[i]->metric;
-        if (m == RF_JARO || m == RF_JARO_WINKLER) continue;
-        if (m == RF_FUZZ_RATIO) {
-            if (op != RF_OP_SIMILARITY && op != RF_OP_NORMALIZED_SIMILARITY) {
-                set_error("RatioBatchComparator only has similarity (fuzz.rs:115-149)");
-                return RF_ERR_INVALID_ARG;
-            }
-        } else if (!norm_op) {
-            set_error("rf_filter_multi_f64: distance and similarity of levenshtein / indel / lcs_seq / osa / damerau_levenshtein are u32-valued (rf_filter_multi_u32)");
-            return RF_ERR_INVALID_ARG;
-        }
-    }
+    rf_args args_v;
+    const rf_args* args = &args_v;
+    if (const rf_status s = check_filter_multi_args("rf_filter_multi_f64", true, cs, q, corpus, op, args_in, capacity, out_index, out_score, out_count, order, &args_v); s != RF_OK) return s;
     if (q == 0) return RF_OK;
-    const rf_args args_v = sanitized_args(args_in, false), *args = &args_v;
-    if (corpus->n != 0)  // what plan() refuses on every road is refused here, before a count is written
-        for (uint32_t i = 0; i < q; ++i)
-            if (const rf_status s = refused_by_plan(cs[i], corpus, op, args, true); s != RF_OK) return s;
-    for (uint32_t i = 0; i < q; ++i) out_count[i] = 0;
-    if (corpus->n == 0) return RF_OK;
-
     FusedFilter fz;
-    if (const rf_status s = filter_multi_fused(true, cs, q, corpus, op, args, capacity, (hipStream_t)stream, &fz); s != RF_OK) return s;
+    if (const rf_status s = filter_multi_fused(true, cs, q, corpus, op, args, capacity, out_count, (hipStream_t)stream, &fz); s != RF_OK) return s;
+    if (corpus->n == 0) return RF_OK;
     // order and decode (rf_filter_multi_rows.hpp); which value a member returns is its plan's op (a fuzz ratio: the similarity)
     uint32_t row = 0;
-    for (const auto& g : fz.groups)
+    for (const auto& g : fz.plan.g.groups)
         for (uint32_t j : g) {
             const uint32_t r = row++;
             const uint32_t count = fz.count(r), have = std::min(count, fz.seg_cap);
@@ -329,7 +246,7 @@ try {
 
     // ---- everything else: the single-query filter, one call per query
     for (uint32_t j = 0; j < q; ++j) {
-        if (fz.taken[j]) continue;
+        if (fz.plan.g.taken[j]) continue;
         const rf_status s = rf_filter_f64(cs[j], corpus, op, args, index_base, capacity, capacity ? out_index + (size_t)j * capacity : nullptr,
                                           capacity ? out_score + (size_t)j * capacity : nullptr, out_count + j, RF_MEM_HOST, order, stream);
         if (s != RF_OK) return s;

@@ -405,19 +405,6 @@ rf_status plan(const rf_comparator* c, const rf_corpus* corpus, rf_op op, const 
     return RF_OK;
 }
 
-// What plan() refuses for (c, corpus, op, args) on every road -- a query beyond what a kernel holds, weights or lengths beyond the u32 results -- asked before
-// anything runs: the multi-query entry points ask it for every query before they write a count, so that a refused call leaves its outputs as they were.
-// (A query that resolve() cannot lower is make_effective()'s, per call; argument errors are the entry points' own.)
-rf_status refused_by_plan(const rf_comparator* c, const rf_corpus* corpus, rf_op op, const rf_args* args, bool f64_out)
-{
-    const rf_comparator* ce = nullptr;
-    ComparatorRef hold;
-    if (resolve(c, corpus, &ce, &hold) != RF_OK) return RF_OK;
-    ScanParams p;
-    RawKind raw = RAW_LEV;
-    return plan(ce, corpus, op, args, f64_out, &p, &raw) == RF_ERR_UNSUPPORTED ? RF_ERR_UNSUPPORTED : RF_OK;
-}
-
 // bytes of per-launch scratch the planned kernels need (0 = none): carry strips of long_kernel, the global DP rows of
 // wf_kernel, the flag strips of jaro_long_kernel -- all handed to the kernels through ScanParams::long_scratch
 static size_t launch_scratch_bytes(const ScanParams& p, RawKind raw)
@@ -1483,30 +1470,22 @@ static rf_status run_many_multi(const rf_comparator* const* cs_in, uint32_t q, c
     char* d_out = static_cast<char*>(out);
     if (out_mem == RF_MEM_HOST) RF_HIP(sc.get(&d_out, row_bytes * q));
 
-    // fusable: single-word Levenshtein / LCS-family recurrences; the group key is what the kernel cannot vary per query
-    // (a tight cutoff is better served by one early-out launch per query than by the fused kernel, which runs every column)
-    auto fusable = [&](uint32_t i) { return (raws[i] == RAW_LEV || raws[i] == RAW_LCS) && cs[i]->words == 1 && !ps[i].long_words_pad && !ps[i].early; };
-    auto same_group = [&](uint32_t a, uint32_t b) {
-        return raws[a] == raws[b] && ps[a].finish == ps[b].finish && ps[a].factor == ps[b].factor && ps[a].op == ps[b].op &&
-               (ps[a].len1 <= 32) == (ps[b].len1 <= 32);
-    };
-    std::vector<char> done(q, 0);
+    // the groups (rf_multi_group.hpp), of contiguous rows of out; a tight cutoff is better served by one early-out launch per query than by the fused kernel,
+    // which runs every column
+    std::vector<MultiQuery> qs(q);
+    for (uint32_t i = 0; i < q; ++i) qs[i] = multi_query(raws[i], cs[i]->words, ps[i], !ps[i].early);
+    const MultiGroups mg = group_queries(qs, (size_t)kMaxMulti, true);
+    size_t next_group = 0;
     rf_status status = RF_OK;
     hipError_t e = hipSuccess;
     for (uint32_t i = 0; i < q && status == RF_OK && e == hipSuccess; ++i) {
-        if (done[i]) continue;
-        std::vector<uint32_t> group{i};
-        if (fusable(i))
-            for (uint32_t j = i + 1; j < q && group.size() < (size_t)kMaxMulti; ++j)
-                if (!done[j] && fusable(j) && same_group(i, j) && j == group.back() + 1) group.push_back(j);  // contiguous rows of out
-        if (group.size() == 3) group.pop_back();
-        for (uint32_t g : group) done[g] = 1;
         ScanParams p = ps[i];
         p.out = d_out + (size_t)i * row_bytes;
-        if (group.size() == 1) {
+        if (!mg.taken[i]) {
             // (through run_many: a general corpus' results take the cheapest way into original order there)
             status = run_many(cs_in[i], corpus, op, args, p.out, RF_MEM_DEVICE, stream, f64_out);
-        } else {
+        } else if (next_group < mg.groups.size() && mg.groups[next_group][0] == i) {  // (the rows behind a group's first are the group's)
+            const std::vector<uint32_t>& group = mg.groups[next_group++];
             p.early = 0;  // the fused kernel always runs every column of every tile (values are the same either way)
             p.tile_begin = 0, p.tile_end = p.n_tiles, p.prefill_none = 0;
             p.multi_q = (uint32_t)group.size();

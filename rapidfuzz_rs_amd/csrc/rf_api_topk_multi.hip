@@ -1,5 +1,7 @@
 // rf_api_topk_multi.hip -- rf_topk_multi_u32 / rf_topk_multi_f64: the k best candidates of each of q queries, fusable queries 4 (then 2) to
 // a pass over the corpus (rf_topk_multi.hip), every other query through rf_topk_u32 / rf_topk_f64 (rf_host.hpp has the shared declarations).
+// Also what the four fused multi-query entry points share (rf_api_filter_multi.hip has the other two): their planner, plan_multi, and the
+// checks of op and members, check_multi_members.
 // Product code: never includes or links anything from oracle/.
 #include "rf_host.hpp"
 
@@ -10,66 +12,124 @@ extern "C" {
 // A/B switch: 0 sends every query down the per-query road (identical results)
 static bool sw_topk_multi() { static const bool v = env_on("RF_TOPK_MULTI"); return v; }
 
-// What rf_topk_multi_u32 and rf_topk_multi_f64 share, after their argument checks: plan every query, group the fusable ones, run the groups
-// and bring their keys home.  `norm` (rf_topk_multi_f64): f64-valued plans, the normalized kernels, and one more condition on a fusable
-// query -- the largest maximum it can meet in this corpus fits the 32-bit score image.
+// Resolves and plans every query once and groups the fusable ones (rf_multi_group.hpp).  What plan() refuses on every road -- a query beyond what a kernel
+// holds, weights or lengths beyond the u32 results -- is refused here, RF_ERR_UNSUPPORTED, at the first such query: the entry points ask before they write
+// a count, so that a refused call leaves its outputs as they were.  A query that resolve() cannot lower (overflow-class symbols need a translated image of
+// the corpus) or that does not plan for another reason is no refusal: it goes to the single-query call, which serves it or reports why not.
+rf_status plan_multi(const MultiAsk& ask, const rf_comparator* const* cs, uint32_t q, const rf_corpus* corpus, rf_op op, const rf_args* args, MultiPlan* out)
+{
+    out->ps.assign(q, ScanParams{});
+    out->raws.assign(q, RAW_LEV);
+    out->eff.assign(q, nullptr);
+    out->holds.assign(q, nullptr);
+    std::vector<MultiQuery> qs(q, MultiQuery{});
+    for (uint32_t i = 0; i < q; ++i) {
+        if (resolve(cs[i], corpus, &out->eff[i], &out->holds[i]) != RF_OK) continue;
+        const ScanParams& p = out->ps[i];
+        const rf_status s = plan(out->eff[i], corpus, op, args, ask.norm, &out->ps[i], &out->raws[i]);
+        if (s == RF_ERR_UNSUPPORTED) return s;
+        if (s != RF_OK || !ask.fuse) continue;
+        qs[i] = multi_query(out->raws[i], out->eff[i]->words, p, (p.early != 0) == ask.early);
+        if (ask.norm && qs[i].fusable) qs[i].fusable = norm_key_fits(p.fin_mS, p.fin_mM, p.len1, corpus->max_len);
+        if (ask.veto && qs[i].fusable) qs[i].fusable = !ask.veto(p, out->raws[i], corpus, ask.norm);
+    }
+    out->g = group_queries(qs, (size_t)kMaxMulti, false);  // (rows are independent here, so unlike run_many_multi's a group's members need not be neighbours)
+    out->fused = 0;
+    for (const auto& g : out->g.groups) out->fused += (uint32_t)g.size();
+    return RF_OK;
+}
+void MultiPlan::trace(const char* road, const std::string& before, const std::string& after) const
+{
+    if (!sw_trace_plan()) return;
+    std::string sizes;
+    for (const auto& grp : g.groups) sizes += (sizes.empty() ? "" : ",") + std::to_string(grp.size());
+    const uint32_t q = (uint32_t)ps.size();
+    std::fprintf(stderr, "[rf plan] %s: q=%u%s fused_groups=[%s] per_query=%u%s\n", road, q, before.c_str(), sizes.c_str(), q - fused, after.c_str());
+}
+
+// The argument checks the four entry points `fn` share, in the order all of them test: op against the result type, then member by member a null comparator
+// before its metric.  `usize_only`: the u32 entry points' text for a metric whose values are f64.
+rf_status check_multi_members(const char* fn, bool f64, const char* usize_only, const rf_comparator* const* cs, uint32_t q, rf_op op)
+{
+    const std::string name(fn);
+    if (!f64 && op != RF_OP_DISTANCE && op != RF_OP_SIMILARITY) {
+        set_error(name + ": op must be RF_OP_DISTANCE or RF_OP_SIMILARITY");
+        return RF_ERR_INVALID_ARG;
+    }
+    if ((int)op < 0 || (int)op > (int)RF_OP_NORMALIZED_SIMILARITY) {
+        set_error("unknown rf_op");
+        return RF_ERR_INVALID_ARG;
+    }
+    const bool norm_op = op == RF_OP_NORMALIZED_DISTANCE || op == RF_OP_NORMALIZED_SIMILARITY;
+    // (a null or unacceptable comparator anywhere in the list is an error whatever q's other members are)
+    for (uint32_t i = 0; i < q; ++i) {
+        if (!cs[i]) {
+            set_error(name + ": null comparator");
+            return RF_ERR_INVALID_ARG;
+        }
+        const rf_metric m = cs[i]->metric;
+        const bool f64_valued = m == RF_JARO || m == RF_JARO_WINKLER || m == RF_FUZZ_RATIO;
+        if (!f64) {
+            if (f64_valued) {
+                set_error(usize_only);
+                return RF_ERR_INVALID_ARG;
+            }
+        } else if (m == RF_FUZZ_RATIO) {
+            if (op != RF_OP_SIMILARITY && op != RF_OP_NORMALIZED_SIMILARITY) {
+                set_error("RatioBatchComparator only has similarity (fuzz.rs:115-149)");
+                return RF_ERR_INVALID_ARG;
+            }
+        } else if (!f64_valued && !norm_op) {
+            set_error(name + ": distance and similarity of levenshtein / indel / lcs_seq / osa / damerau_levenshtein are u32-valued (" + name.substr(0, name.size() - 3) + "u32)");
+            return RF_ERR_INVALID_ARG;
+        }
+    }
+    return RF_OK;
+}
+// ... and the top-k family's: everything is decided before the corpus is looked at or a device is touched.  Nothing is written before every output is known to be
+// there; like rf_many_multi_*, only a non-empty corpus needs the row arrays, and q == 0 -- which writes nothing -- needs none.
+static rf_status check_topk_multi_args(const char* fn, bool f64, const rf_comparator* const* cs, uint32_t q, const rf_corpus* corpus, rf_op op, const rf_args* args_in, uint32_t k,
+                                       const void* out_score, const uint64_t* out_index, const uint32_t* out_count, rf_args* args)
+{
+    if (!cs || !corpus || !args_in) {
+        set_error(std::string(fn) + ": null handle or args");
+        return RF_ERR_INVALID_ARG;
+    }
+    if (k == 0) {
+        set_error("top-k: k must be at least 1");
+        return RF_ERR_INVALID_ARG;
+    }
+    if (const rf_status s = check_multi_members(fn, f64, "top-k: usize-valued metrics only (jaro / jaro_winkler / fuzz ratio: rf_topk_f64)", cs, q, op); s != RF_OK) return s;
+    if (q != 0 && (!out_count || (corpus->n != 0 && (!out_score || !out_index)))) {
+        set_error(std::string(fn) + ": null output");
+        return RF_ERR_INVALID_ARG;
+    }
+    *args = sanitized_args(args_in, false);
+    return RF_OK;
+}
+
+// What rf_topk_multi_u32 and rf_topk_multi_f64 share, after their argument checks: plan every query (a refusal comes before a count is written), run the
+// fused groups and bring their keys home.  `norm` (rf_topk_multi_f64): f64-valued plans and the normalized kernels.  Fused: plans without a tight cutoff (a
+// head-plane early-out scan per query is far faster than any fused full scan), k <= 64.
 struct FusedTopk {
-    std::vector<std::vector<uint32_t>> groups;  // members of each fused group, as indices into cs
-    std::vector<char> taken;                    // [q] 1: the query is in a group
-    std::vector<uint64_t> keys;                 // [fused rows in group order][k], best first, ~0 = empty
+    MultiPlan plan;
+    std::vector<uint64_t> keys;  // [fused rows in group order][k], best first, ~0 = empty
 };
 static rf_status topk_multi_fused(bool norm, const rf_comparator* const* cs, uint32_t q, const rf_corpus* corpus, rf_op op, const rf_args* args, uint32_t k,
-                                  hipStream_t st, FusedTopk* out)
+                                  uint32_t* out_count, hipStream_t st, FusedTopk* out)
 {
-    // ---- plan every query; which ones can be fused
-    std::vector<ScanParams> ps(q);
-    std::vector<RawKind> raws(q, RAW_LEV);
-    std::vector<const rf_comparator*> eff(q, nullptr);
-    std::vector<ComparatorRef> holds(q);
-    std::vector<char> fusable(q, 0);
-    if (sw_topk_multi() && k <= (uint32_t)kWave)
-        for (uint32_t i = 0; i < q; ++i) {
-            // (a query that does not resolve -- overflow-class symbols need a translated image of the corpus -- or does not plan goes to
-            // the single-query call, which serves it or reports why not)
-            if (resolve(cs[i], corpus, &eff[i], &holds[i]) != RF_OK) continue;
-            if (plan(eff[i], corpus, op, args, norm, &ps[i], &raws[i]) != RF_OK) continue;
-            fusable[i] = (raws[i] == RAW_LEV || raws[i] == RAW_LCS) && eff[i]->words == 1 && !ps[i].long_words_pad && !ps[i].early;
-            if (norm && fusable[i]) {
-                // the 32-bit score image (rf_norm_key.hpp) is exact while every maximum of the scan is <= 65535; the maximum grows with the candidate's length
-                const uint64_t len1 = ps[i].len1, len2 = corpus->max_len;
-                const uint64_t largest = (uint64_t)ps[i].fin_mS * (len1 + len2) + (uint64_t)ps[i].fin_mM * std::max(len1, len2);
-                fusable[i] = largest <= kNormKeyMaxMaximum;
-            }
-        }
-    // (ps[].op: what the kernel computes -- a fuzz ratio plans to RF_OP_NORMALIZED_SIMILARITY whichever similarity op was asked for)
-    auto same_group = [&](uint32_t a, uint32_t b) {
-        return raws[a] == raws[b] && ps[a].finish == ps[b].finish && ps[a].factor == ps[b].factor && ps[a].op == ps[b].op &&
-               (ps[a].len1 <= 32) == (ps[b].len1 <= 32);
-    };
-    // (rows are independent here, so unlike run_many_multi's a group's members need not be neighbours)
-    std::vector<std::vector<uint32_t>>& groups = out->groups;
-    std::vector<char>& taken = out->taken;
-    taken.assign(q, 0);
-    for (uint32_t i = 0; i < q; ++i) {
-        if (taken[i] || !fusable[i]) continue;
-        std::vector<uint32_t> g{i};
-        for (uint32_t j = i + 1; j < q && g.size() < (size_t)kMaxMulti; ++j)
-            if (!taken[j] && fusable[j] && same_group(i, j)) g.push_back(j);
-        if (g.size() == 3) g.pop_back();
-        if (g.size() < 2) continue;  // the odd one left over
-        for (uint32_t m : g) taken[m] = 1;
-        groups.push_back(std::move(g));
-    }
-    uint32_t fused = 0;
-    for (const auto& g : groups) fused += (uint32_t)g.size();
+    MultiPlan& mp = out->plan;
+    if (corpus->n != 0)
+        if (const rf_status s = plan_multi(MultiAsk{norm, false, sw_topk_multi() && k <= (uint32_t)kWave, nullptr}, cs, q, corpus, op, args, &mp); s != RF_OK) return s;
+    for (uint32_t i = 0; i < q; ++i) out_count[i] = 0;
+    if (corpus->n == 0) return RF_OK;
+    const std::vector<ScanParams>& ps = mp.ps;
+    const std::vector<std::vector<uint32_t>>& groups = mp.g.groups;
+    const uint32_t fused = mp.fused;
     const uint32_t n_tiles = corpus->n_tiles;
     const uint32_t sample_tiles = sw_topk_sample();
     const bool sample = !groups.empty() && sample_tiles && n_tiles >= 8 * sample_tiles;  // topk_core's rule (a fused group never has a tight cutoff)
-    if (sw_trace_plan()) {
-        std::string sizes;
-        for (const auto& g : groups) sizes += (sizes.empty() ? "" : ",") + std::to_string(g.size());
-        std::fprintf(stderr, "[rf plan] %s: q=%u k=%u fused_groups=[%s] per_query=%u sample=%d\n", norm ? "topk_multi_f64" : "topk_multi", q, k, sizes.c_str(), q - fused, sample ? 1 : 0);
-    }
+    mp.trace(norm ? "topk_multi_f64" : "topk_multi", " k=" + std::to_string(k), sample ? " sample=1" : " sample=0");
 
     // ---- the fused groups: everything enqueued, one copy home
     std::vector<uint64_t>& keys = out->keys;
@@ -109,7 +169,7 @@ static rf_status topk_multi_fused(bool norm, const rf_comparator* const* cs, uin
             p.key_index_base = 0;  // index_base is added on the host, in 64 bits
             for (size_t m = 0; m < g.size() && status == RF_OK; ++m) {
                 p.multi_len1[m] = ps[g[m]].len1;
-                status = comparator_device_pm(eff[g[m]], corpus->device, &p.multi_pm[m]);
+                status = comparator_device_pm(mp.eff[g[m]], corpus->device, &p.multi_pm[m]);
             }
             if (status != RF_OK) break;
             tp.bound = reinterpret_cast<uint64_t*>(ctl);
@@ -123,10 +183,10 @@ static rf_status topk_multi_fused(bool norm, const rf_comparator* const* cs, uin
                 TopkMultiParams ts = tp;
                 ts.s.tile_step = n_tiles / sample_tiles;
                 ts.sample = 1;
-                e = launch_topk_multi(raws[i], narrow, ts, st);
+                e = launch_topk_multi(mp.raws[i], narrow, ts, st);
                 if (e == hipSuccess) e = launch_topk_multi_select(ts, nullptr, st);
             }
-            if (e == hipSuccess) e = launch_topk_multi(raws[i], narrow, tp, st);
+            if (e == hipSuccess) e = launch_topk_multi(mp.raws[i], narrow, tp, st);
             if (e == hipSuccess) e = launch_topk_multi_select(tp, d_keys + (size_t)row * k, st);
             if (e != hipSuccess) break;
             row += (uint32_t)g.size();
@@ -154,51 +214,18 @@ static rf_status topk_multi_fused(bool norm, const rf_comparator* const* cs, uin
 rf_status rf_topk_multi_u32(const rf_comparator* const* cs, uint32_t q, const rf_corpus* corpus, rf_op op, const rf_args* args_in, uint32_t k,
                             uint64_t index_base, uint32_t* out_score, uint64_t* out_index, uint32_t* out_count, void* stream)
 try {
-    // ---- arguments: everything here is decided before the corpus is looked at or a device is touched
-    if (!cs || !corpus || !args_in) {
-        set_error("rf_topk_multi_u32: null handle or args");
-        return RF_ERR_INVALID_ARG;
-    }
-    if (k == 0) {
-        set_error("top-k: k must be at least 1");
-        return RF_ERR_INVALID_ARG;
-    }
-    if (op != RF_OP_DISTANCE && op != RF_OP_SIMILARITY) {
-        set_error("rf_topk_multi_u32: op must be RF_OP_DISTANCE or RF_OP_SIMILARITY");
-        return RF_ERR_INVALID_ARG;
-    }
+    rf_args args_v;
+    const rf_args* args = &args_v;
+    if (const rf_status s = check_topk_multi_args("rf_topk_multi_u32", false, cs, q, corpus, op, args_in, k, out_score, out_index, out_count, &args_v); s != RF_OK) return s;
     if (q == 0) return RF_OK;
-    for (uint32_t i = 0; i < q; ++i) {
-        if (!cs[i]) {
-            set_error("rf_topk_multi_u32: null comparator");
-            return RF_ERR_INVALID_ARG;
-        }
-        if (cs[i]->metric == RF_JARO || cs[i]->metric == RF_JARO_WINKLER || cs[i]->metric == RF_FUZZ_RATIO) {
-            set_error("top-k: usize-valued metrics only (jaro / jaro_winkler / fuzz ratio: rf_topk_f64)");
-            return RF_ERR_INVALID_ARG;
-        }
-    }
-    // (nothing is written before every output is known to be there; like rf_many_multi_*, only a non-empty corpus needs the row arrays)
-    if (!out_count || (corpus->n != 0 && (!out_score || !out_index))) {
-        set_error("rf_topk_multi_u32: null output");
-        return RF_ERR_INVALID_ARG;
-    }
-    const rf_args args_v = sanitized_args(args_in, false), *args = &args_v;
-    if (corpus->n != 0)  // what plan() refuses on every road is refused here, before a count is written
-        for (uint32_t i = 0; i < q; ++i)
-            if (const rf_status s = refused_by_plan(cs[i], corpus, op, args, false); s != RF_OK) return s;
-    for (uint32_t i = 0; i < q; ++i) out_count[i] = 0;
-    if (corpus->n == 0) return RF_OK;
-
     FusedTopk fz;
-    if (const rf_status s = topk_multi_fused(false, cs, q, corpus, op, args, k, (hipStream_t)stream, &fz); s != RF_OK) return s;
-    const std::vector<std::vector<uint32_t>>& groups = fz.groups;
-    const std::vector<char>& taken = fz.taken;
+    if (const rf_status s = topk_multi_fused(false, cs, q, corpus, op, args, k, out_count, (hipStream_t)stream, &fz); s != RF_OK) return s;
+    if (corpus->n == 0) return RF_OK;
     const std::vector<uint64_t>& keys = fz.keys;
     // decode as rf_topk_u32 does
     const bool desc = op == RF_OP_SIMILARITY;
     uint32_t row = 0;
-    for (const auto& g : groups)
+    for (const auto& g : fz.plan.g.groups)
         for (uint32_t j : g) {
             const uint64_t* best = keys.data() + (size_t)row++ * k;
             uint32_t m = 0;
@@ -212,7 +239,7 @@ try {
 
     // ---- everything else: the single-query top-k, one call per query
     for (uint32_t j = 0; j < q; ++j) {
-        if (taken[j]) continue;
+        if (fz.plan.g.taken[j]) continue;
         const rf_status s = rf_topk_u32(cs[j], corpus, op, args, k, index_base, out_score + (size_t)j * k, out_index + (size_t)j * k, out_count + j, nullptr, RF_MEM_HOST, stream);
         if (s != RF_OK) return s;
     }
@@ -232,55 +259,16 @@ RF_ABI_CATCH
 rf_status rf_topk_multi_f64(const rf_comparator* const* cs, uint32_t q, const rf_corpus* corpus, rf_op op, const rf_args* args_in, uint32_t k,
                             uint64_t index_base, double* out_score, uint64_t* out_index, uint32_t* out_count, void* stream)
 try {
-    // ---- arguments: everything here is decided before the corpus is looked at or a device is touched
-    if (!cs || !corpus || !args_in) {
-        set_error("rf_topk_multi_f64: null handle or args");
-        return RF_ERR_INVALID_ARG;
-    }
-    if (k == 0) {
-        set_error("top-k: k must be at least 1");
-        return RF_ERR_INVALID_ARG;
-    }
-    if ((int)op < 0 || (int)op > (int)RF_OP_NORMALIZED_SIMILARITY) {
-        set_error("unknown rf_op");
-        return RF_ERR_INVALID_ARG;
-    }
+    rf_args args_v;
+    const rf_args* args = &args_v;
+    if (const rf_status s = check_topk_multi_args("rf_topk_multi_f64", true, cs, q, corpus, op, args_in, k, out_score, out_index, out_count, &args_v); s != RF_OK) return s;
     if (q == 0) return RF_OK;
-    const bool norm_op = op == RF_OP_NORMALIZED_DISTANCE || op == RF_OP_NORMALIZED_SIMILARITY;
-    for (uint32_t i = 0; i < q; ++i) {
-        if (!cs[i]) {
-            set_error("rf_topk_multi_f64: null comparator");
-            return RF_ERR_INVALID_ARG;
-        }
-        const rf_metric m = cs[i]->metric;
-        if (m == RF_JARO || m == RF_JARO_WINKLER) continue;
-        if (m == RF_FUZZ_RATIO) {
-            if (op != RF_OP_SIMILARITY && op != RF_OP_NORMALIZED_SIMILARITY) {
-                set_error("RatioBatchComparator only has similarity (fuzz.rs:115-149)");
-                return RF_ERR_INVALID_ARG;
-            }
-        } else if (!norm_op) {
-            set_error("rf_topk_multi_f64: distance and similarity of levenshtein / indel / lcs_seq / osa / damerau_levenshtein are u32-valued (rf_topk_multi_u32)");
-            return RF_ERR_INVALID_ARG;
-        }
-    }
-    // (nothing is written before every output is known to be there; only a non-empty corpus needs the row arrays)
-    if (!out_count || (corpus->n != 0 && (!out_score || !out_index))) {
-        set_error("rf_topk_multi_f64: null output");
-        return RF_ERR_INVALID_ARG;
-    }
-    const rf_args args_v = sanitized_args(args_in, false), *args = &args_v;
-    if (corpus->n != 0)  // what plan() refuses on every road is refused here, before a count is written
-        for (uint32_t i = 0; i < q; ++i)
-            if (const rf_status s = refused_by_plan(cs[i], corpus, op, args, true); s != RF_OK) return s;
-    for (uint32_t i = 0; i < q; ++i) out_count[i] = 0;
-    if (corpus->n == 0) return RF_OK;
-
     FusedTopk fz;
-    if (const rf_status s = topk_multi_fused(true, cs, q, corpus, op, args, k, (hipStream_t)stream, &fz); s != RF_OK) return s;
+    if (const rf_status s = topk_multi_fused(true, cs, q, corpus, op, args, k, out_count, (hipStream_t)stream, &fz); s != RF_OK) return s;
+    if (corpus->n == 0) return RF_OK;
     // decode: the key's fraction is the normalized distance; which value the member returns is its plan's op (a fuzz ratio: the similarity)
     uint32_t row = 0;
-    for (const auto& g : fz.groups)
+    for (const auto& g : fz.plan.g.groups)
         for (uint32_t j : g) {
             const bool as_distance = op == RF_OP_NORMALIZED_DISTANCE && cs[j]->metric != RF_FUZZ_RATIO;
             const uint64_t* best = fz.keys.data() + (size_t)row++ * k;
@@ -296,7 +284,7 @@ try {
 
     // ---- everything else: the single-query top-k, one call per query
     for (uint32_t j = 0; j < q; ++j) {
-        if (fz.taken[j]) continue;
+        if (fz.plan.g.taken[j]) continue;
         uint64_t count = 0;
         const rf_status s = rf_topk_f64(cs[j], corpus, op, args, k, index_base, out_score + (size_t)j * k, out_index + (size_t)j * k, &count, nullptr, RF_MEM_HOST, stream);
         if (s != RF_OK) return s;

@@ -617,6 +617,25 @@ __device__ __forceinline__ uint32_t usize_value(const ScanParams& p, uint32_t ra
     return usize_value(p, tile_fin(p, len1, len2), raw, keep);
 }
 
+// The normalized ops' f64 rule, ONCE: every kernel that keeps or drops a RESULT by an f64 cutoff -- emit_fin, the fused multi-query kernels of
+// rf_topk_multi.hip / rf_filter_multi.hip -- does it by these two, so a cutoff that equals a score falls the same way on every road.
+// may_pass, the early-out look, takes norm_dist and spells the compare itself (see there).
+// details/distance.rs:246-250: dist / maximum (0.0 when maximum == 0)
+struct NormDist {
+    uint32_t dist;
+    double nd;
+};
+// (norm_dist in two halves, for topk_multi_kernel: it needs dist for every candidate and the quotient -- a division -- under a cutoff only)
+__device__ __forceinline__ uint32_t fin_dist(const ScanParams& p, const TileFin& f, uint32_t raw) { return f.d0 + (uint32_t)p.fin_dR * raw; }
+__device__ __forceinline__ double norm_of(uint32_t dist, uint32_t max) { return max == 0 ? 0.0 : (double)dist / (double)max; }
+__device__ __forceinline__ NormDist norm_dist(const ScanParams& p, const TileFin& f, uint32_t raw)
+{
+    const uint32_t dist = fin_dist(p, f, raw);
+    return NormDist{dist, norm_of(dist, f.max)};
+}
+// details/distance.rs:273: the similarity is 1.0 - norm_dist, computed and THEN compared (never nd <= 1.0 - cutoff: that rounds elsewhere)
+__device__ __forceinline__ bool norm_keep(const ScanParams& p, double nd) { return p.op == RF_OP_NORMALIZED_DISTANCE ? nd <= p.cutoff_f64 : (1.0 - nd) >= p.cutoff_f64; }
+
 // one result from a tile's finishing terms; `out` is the launch's (or, in the multi-query kernel, the query's) row
 __device__ __forceinline__ void emit_fin(const ScanParams& p, const TileFin& f, uint32_t raw, uint32_t idx, void* out)
 {
@@ -625,17 +644,17 @@ __device__ __forceinline__ void emit_fin(const ScanParams& p, const TileFin& f, 
         const uint32_t v = usize_value(p, f, raw, &keep);
         reinterpret_cast<uint32_t*>(out)[idx] = keep ? v : RF_NONE_U32;
     } else {
-        const uint32_t dist = f.d0 + (uint32_t)p.fin_dR * raw;
-        // details/distance.rs:246-250: dist / maximum (0.0 when maximum == 0)
-        const double nd = f.max == 0 ? 0.0 : (double)dist / (double)f.max;
+        const double nd = norm_dist(p, f, raw).nd;
+        // (the op picks the stored value, and each arm asks norm_keep on its own: inside an arm the helper folds to the one compare of `v`, which is the code the
+        // single-query kernels have always had -- one `keep` behind the arms compiles to a different branch structure in every kernel that emits f64)
         double v;
         bool keep;
         if (p.op == RF_OP_NORMALIZED_DISTANCE) {
             v = nd;
-            keep = !p.has_cutoff || v <= p.cutoff_f64;
-        } else {  // details/distance.rs:273: 1.0 - norm_dist
+            keep = !p.has_cutoff || norm_keep(p, nd);
+        } else {
             v = 1.0 - nd;
-            keep = !p.has_cutoff || v >= p.cutoff_f64;
+            keep = !p.has_cutoff || norm_keep(p, nd);
         }
         reinterpret_cast<double*>(out)[idx] = keep ? v : __longlong_as_double(0x7FF8000000000000ll);
     }
@@ -651,11 +670,12 @@ __device__ __forceinline__ void emit_usize(const ScanParams& p, uint32_t raw, ui
 __device__ __forceinline__ bool may_pass(const ScanParams& p, const TileFin& f, uint32_t raw_bound)
 {
     bool keep;
-    if (!p.out_f64) {
+    if (!p.out_f64)
         (void)usize_value(p, f, raw_bound, &keep);
-    } else {
-        const uint32_t dist = f.d0 + (uint32_t)p.fin_dR * raw_bound;
-        const double nd = f.max == 0 ? 0.0 : (double)dist / (double)f.max;
+    else {
+        // (norm_keep's compare, spelled in place: behind a call the compiler turns the uniform branch on the op into a select of both compares in every cutoff
+        // kernel, and the fused f64 filter measured 3-4 % slower with it at 10 M candidates.  tests/test_gpu_cutoff_edges.py holds the two together.)
+        const double nd = norm_dist(p, f, raw_bound).nd;
         keep = p.op == RF_OP_NORMALIZED_DISTANCE ? nd <= p.cutoff_f64 : (1.0 - nd) >= p.cutoff_f64;
     }
     return keep;
@@ -1077,6 +1097,56 @@ __device__ __forceinline__ TileView load_tile(const ScanParams& p, uint32_t t)
     return v;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// What the fused multi-query kernels share (scan_multi_kernel, topk_multi_kernel, filter_multi_kernel): Q single-word tables side by side in LDS,
+// one candidate per lane, Q recurrence states per lane.  (Each keeps its own tile walk: one shared function for the two full scans changed the register
+// allocation of topk_multi_kernel -- the occupancy of two instantiations -- and its 10 M shapes measured 4-6 % slower.)
+// ---------------------------------------------------------------------------------------------------
+// the Q tables into LDS, table row c at row sigma(c) (whole workgroup; synchronizes)
+template <class Word, int Q>
+__device__ __forceinline__ void fill_multi_tables(Word (&lds_pm)[Q][256], const ScanParams& p)
+{
+    for (int i = threadIdx.x; i < Q * 256; i += kWave * kWavesPerBlock) {
+        const int q = i / 256, c = i % 256;
+        lds_pm[q][p.sigma[c]] = (Word)p.multi_pm[q][c];  // single-word tables: row stride 1
+    }
+    __syncthreads();
+}
+// The counted append: the passing lanes of a wavefront take neighbouring places behind *count -- one atomic, by lane 0 -- and store their keys in `seg` while
+// their place is below seg_cap; the counter counts on beyond it.  key() is evaluated behind the ballot, by the wavefronts that hold a passer.
+template <class Key>
+__device__ __forceinline__ void append_passers(uint32_t* count, uint64_t* seg, uint32_t seg_cap, bool pass, uint32_t lane, Key&& key)
+{
+    const uint64_t m = __ballot(pass);
+    if (!m) return;
+    uint32_t base = 0;
+    if (lane == 0) base = atomicAdd(count, (uint32_t)__popcll(m));
+    base = uniform(base);
+    const uint32_t at = base + (uint32_t)__popcll(m & ((1ull << lane) - 1));
+    const uint64_t mine = key();
+    if (pass && at < seg_cap) seg[at] = mine;
+}
+// Host side: the instantiation of a fused kernel for (raw: RAW_LEV or RAW_LCS; narrow: every query <= 32 symbols; multi_q: 2 or 4; p.tiles: tile descriptors or a
+// single-length corpus).  launch(state, q, uniform) gets the three as types: typename decltype(state)::type, decltype(q)::value, decltype(uniform)::value.
+template <class T>
+struct MultiStateTag {
+    using type = T;
+};
+template <class Launch>
+hipError_t dispatch_multi(RawKind raw, bool narrow, const ScanParams& p, Launch&& launch)
+{
+    auto with_state = [&](auto state) {
+        auto with_q = [&](auto q) { return p.tiles ? launch(state, q, std::false_type{}) : launch(state, q, std::true_type{}); };
+        switch (p.multi_q) {
+        case 2: return with_q(std::integral_constant<int, 2>{});
+        case 4: return with_q(std::integral_constant<int, 4>{});
+        default: return hipErrorInvalidValue;
+        }
+    };
+    if (raw == RAW_LEV) return narrow ? with_state(MultiStateTag<Lev32State>{}) : with_state(MultiStateTag<LevState<1>>{});
+    if (raw == RAW_LCS) return narrow ? with_state(MultiStateTag<Lcs32State>{}) : with_state(MultiStateTag<LcsState<1>>{});
+    return hipErrorInvalidValue;
+}
 
 // The row-DP kernels (rf_long.hip wf_kernel, rf_damerau.hip dl_kernel) compare symbols, not table rows: the query, renamed like the
 // corpus, rebuilt from the PM table into `qwords` words of LDS, 4 symbols per word (whole workgroup; synchronizes).

@@ -23,7 +23,7 @@ namespace rf {
 // base + rank while that is below seg_cap.  The counter counts on beyond seg_cap: it is the true number of matches.  Under a tight cutoff
 // passers are rare, so the atomics are (the planner fuses p.early queries only).
 // kNorm (rf_filter_multi_f64): the normalized ops.  p.out_f64 is set, so the looks already run may_pass()'s f64 arithmetic; at a tile's end `keep` is
-// emit_fin's f64 compare to the letter -- nd = dist / maximum against p.cutoff_f64, an arbitrary double -- and never a compare on keys.  What is stored is
+// emit_fin's f64 compare (norm_dist / norm_keep, rf_device.hpp) -- nd = dist / maximum against p.cutoff_f64, an arbitrary double -- and never a compare on keys.  What is stored is
 // the key's image of nd, norm_key(dist, maximum) (rf_norm_key.hpp): ascending for both ops (a smaller key is the better score), so topk_desc is not read.
 // f64 cost: the division of the compare is paid per lane, but only by a member that is still live at its tile's end; the maximum is uniform per member
 // and tile, and its scale -- the second f64 division -- is computed behind the ballot, by wavefronts that hold a passer.
@@ -31,16 +31,11 @@ namespace rf {
 template <class State, int Q, bool kUniform, bool kNorm>
 __global__ __launch_bounds__(kWave* kWavesPerBlock) void filter_multi_kernel(const FilterMultiParams fp)
 {
-    using Word = typename State::Word;
     static_assert(State::kWords == 1, "multi-query kernels are single-word");
     static_assert(State::kCanPrune, "the fused cutoff scan needs a state with a bound");
     const ScanParams& p = fp.s;
-    __shared__ Word lds_pm[Q][256];
-    for (int i = threadIdx.x; i < Q * 256; i += kWave * kWavesPerBlock) {
-        const int q = i / 256, c = i % 256;
-        lds_pm[q][p.sigma[c]] = (Word)p.multi_pm[q][c];  // single-word tables: row stride 1
-    }
-    __syncthreads();
+    __shared__ typename State::Word lds_pm[Q][256];
+    fill_multi_tables(lds_pm, p);
 
     const uint32_t lane = threadIdx.x & (kWave - 1);
     const uint32_t wave = uniform(threadIdx.x / kWave);
@@ -105,34 +100,19 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void filter_multi_kernel(con
         for (int q = 0; q < Q; ++q) {
             if (!(live & (1u << q))) continue;
             const uint32_t raw = st[q].result(p.multi_len1[q], len2);
+            uint32_t* count = fp.count + q * kFilterMultiLine32;
+            uint64_t* seg = fp.cand + (size_t)q * fp.seg_cap;
             if constexpr (!kNorm) {
                 bool keep;
                 const uint32_t v = usize_value(p, fin[q], raw, &keep);
-                const bool pass = valid && keep;
-                const uint64_t m = __ballot(pass);
-                if (m) {
-                    uint32_t base = 0;
-                    if (lane == 0) base = atomicAdd(fp.count + q * kFilterMultiLine32, (uint32_t)__popcll(m));
-                    base = uniform(base);
-                    const uint32_t at = base + (uint32_t)__popcll(m & ((1ull << lane) - 1));
-                    if (pass && at < fp.seg_cap) fp.cand[(size_t)q * fp.seg_cap + at] = ((uint64_t)(p.topk_desc ? ~v : v) << 32) | idx;
-                }
+                append_passers(count, seg, fp.seg_cap, valid && keep, lane, [&] { return ((uint64_t)(p.topk_desc ? ~v : v) << 32) | idx; });
             } else {
-                // emit_fin's f64 branch, to the letter (has_cutoff: the launcher takes plans under a cutoff only)
-                const uint32_t fmax = uniform(fin[q].max);
-                const uint32_t dist = fin[q].d0 + (uint32_t)p.fin_dR * raw;
-                const double nd = fmax == 0 ? 0.0 : (double)dist / (double)fmax;
-                const bool keep = p.op == RF_OP_NORMALIZED_DISTANCE ? nd <= p.cutoff_f64 : (1.0 - nd) >= p.cutoff_f64;
-                const bool pass = valid && keep;
-                const uint64_t m = __ballot(pass);
-                if (m) {
-                    uint32_t base = 0;
-                    if (lane == 0) base = atomicAdd(fp.count + q * kFilterMultiLine32, (uint32_t)__popcll(m));
-                    base = uniform(base);
-                    const uint32_t at = base + (uint32_t)__popcll(m & ((1ull << lane) - 1));
-                    const double scale = norm_key_scale(fmax);  // (one division per tile and member, wavefront-uniform, behind the ballot)
-                    if (pass && at < fp.seg_cap) fp.cand[(size_t)q * fp.seg_cap + at] = ((uint64_t)norm_key_scaled(dist, fmax, scale) << 32) | idx;
-                }
+                // (has_cutoff: the launcher takes plans under a cutoff only)
+                TileFin f = fin[q];
+                f.max = uniform(f.max);
+                const NormDist d = norm_dist(p, f, raw);
+                // (the key's scale: one division per tile and member, wavefront-uniform, behind the ballot)
+                append_passers(count, seg, fp.seg_cap, valid && norm_keep(p, d.nd), lane, [&] { return ((uint64_t)norm_key_scaled(d.dist, f.max, norm_key_scale(f.max)) << 32) | idx; });
             }
         }
 
@@ -140,31 +120,6 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void filter_multi_kernel(con
         cur = ahead;  // dead, empty or walked to its end: the next tile starts from the prefetched chunk
         t = t_next;
         cur_tile = next_tile;
-    }
-}
-
-template <class State, int Q>
-static hipError_t launch_filter_multi_q(const FilterMultiParams& fp, hipStream_t stream, int grid)
-{
-    const dim3 g(grid), b(kWave * kWavesPerBlock);
-    if (fp.norm) {
-        if (fp.s.tiles)
-            hipLaunchKernelGGL((filter_multi_kernel<State, Q, false, true>), g, b, 0, stream, fp);
-        else
-            hipLaunchKernelGGL((filter_multi_kernel<State, Q, true, true>), g, b, 0, stream, fp);
-    } else if (fp.s.tiles)
-        hipLaunchKernelGGL((filter_multi_kernel<State, Q, false, false>), g, b, 0, stream, fp);
-    else
-        hipLaunchKernelGGL((filter_multi_kernel<State, Q, true, false>), g, b, 0, stream, fp);
-    return hipGetLastError();
-}
-template <class State>
-static hipError_t launch_filter_multi_state(const FilterMultiParams& fp, hipStream_t stream, int grid)
-{
-    switch (fp.s.multi_q) {
-    case 2: return launch_filter_multi_q<State, 2>(fp, stream, grid);
-    case 4: return launch_filter_multi_q<State, 4>(fp, stream, grid);
-    default: return hipErrorInvalidValue;
     }
 }
 
@@ -177,10 +132,15 @@ hipError_t launch_filter_multi(RawKind raw, bool narrow, const FilterMultiParams
     if (!fp.count || (fp.seg_cap && !fp.cand) || p.tile_end > p.n_tiles) return hipErrorInvalidValue;
     if (fp.norm ? !(p.out_f64 && p.has_cutoff && (p.op == RF_OP_NORMALIZED_DISTANCE || p.op == RF_OP_NORMALIZED_SIMILARITY)) : p.out_f64 != 0) return hipErrorInvalidValue;
     if (p.tile_end <= p.tile_begin) return hipSuccess;
-    const int grid = std::max(1, scan_grid(p.tile_end - p.tile_begin));
-    if (raw == RAW_LEV) return narrow ? launch_filter_multi_state<Lev32State>(fp, stream, grid) : launch_filter_multi_state<LevState<1>>(fp, stream, grid);
-    if (raw == RAW_LCS) return narrow ? launch_filter_multi_state<Lcs32State>(fp, stream, grid) : launch_filter_multi_state<LcsState<1>>(fp, stream, grid);
-    return hipErrorInvalidValue;
+    const dim3 g(std::max(1, scan_grid(p.tile_end - p.tile_begin))), b(kWave * kWavesPerBlock);
+    return dispatch_multi(raw, narrow, p, [&](auto state, auto q, auto uniform) {
+        using State = typename decltype(state)::type;
+        if (fp.norm)
+            hipLaunchKernelGGL((filter_multi_kernel<State, decltype(q)::value, decltype(uniform)::value, true>), g, b, 0, stream, fp);
+        else
+            hipLaunchKernelGGL((filter_multi_kernel<State, decltype(q)::value, decltype(uniform)::value, false>), g, b, 0, stream, fp);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace rf

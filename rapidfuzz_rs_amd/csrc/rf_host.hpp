@@ -3,6 +3,7 @@
 //   rf_api_scan.hip   plan(): Args x metric x op -> kernel parameters; rf_many_* / rf_one_* / rf_many_multi_* and what they launch
 //   rf_api_topk.hip   top-k: in-scan lists, selection, 8-byte keys and 16-byte entries, the RCCL exchange
 //   rf_api_files.hip  corpus files (save / load / validate) and streamed scans
+//   rf_api_topk_multi.hip, rf_api_filter_multi.hip  the fused multi-query calls; their one planner (MultiPlan, plan_multi) is declared below
 // Host code only; nothing here is visible outside librfgpu.so.
 #pragma once
 #include <dlfcn.h>
@@ -29,6 +30,8 @@
 #include <vector>
 
 #include "rf_internal.hpp"
+#include "rf_multi_group.hpp"
+#include "rf_norm_key.hpp"
 
 namespace rf {
 
@@ -471,6 +474,29 @@ static inline uint64_t tile_bytes(uint32_t len) { return (uint64_t)((len + kChun
         return RF_ERR_INVALID_ARG;                                                                      \
     }
 
+// ---- the planner of rf_topk_multi_* / rf_filter_multi_* (rf_api_topk_multi.hip plan_multi): every query resolved and planned ONCE, the fusable ones grouped
+static_assert(RAW_LEV == kMultiRawLev && RAW_LCS == kMultiRawLcs, "rf_multi_group.hpp names the two kinds by value");
+inline MultiQuery multi_query(RawKind raw, uint32_t words, const ScanParams& p, bool fusable)
+{
+    return MultiQuery{fusable && fusable_base(raw, words, p.long_words_pad), MultiGroupKey{raw, p.finish, p.factor, p.op, p.len1 <= 32}};
+}
+struct MultiAsk {
+    bool norm;         // f64-valued plans; a fusable query also keeps every maximum of its scan within the 32-bit score image (norm_key_fits)
+    bool early;        // fuse the plans with this `early`: under a tight cutoff (rf_filter_multi_*) or without one (rf_topk_multi_*)
+    bool fuse;         // the caller's switches: false sends every query per query (it is planned all the same)
+    bool (*veto)(const ScanParams& p, RawKind raw, const rf_corpus* corpus, bool norm);  // a fusable query the caller still wants per query, or nullptr
+};
+struct MultiPlan {
+    std::vector<ScanParams> ps;             // [q] the plans (of the queries that resolved and planned: only a fused member's is read)
+    std::vector<RawKind> raws;              // [q]
+    std::vector<const rf_comparator*> eff;  // [q] the comparators lowered to the corpus' ids
+    std::vector<ComparatorRef> holds;       // [q] ... and what keeps them alive
+    MultiGroups g;                          // the fused groups as indices into cs, and who is in one
+    uint32_t fused = 0;                     // members of all groups: the fused rows, in group order
+    // "[rf plan] <road>: q=<q><before> fused_groups=[4,2] per_query=<n><after>" on stderr under RF_TRACE_PLAN
+    void trace(const char* road, const std::string& before, const std::string& after) const;
+};
+
 // ---- shared between the translation units (definitions: the file named in the comment; they sit inside the files' extern "C" blocks)
 #pragma clang diagnostic ignored "-Wreturn-type-c-linkage"
 // (hidden: these are internal to librfgpu.so -- only the rf_* entry points of include/rfgpu.h are exported)
@@ -484,7 +510,8 @@ RF_LOCAL size_t pm_stride(const rf_comparator* c);                              
 RF_LOCAL rf_status comparator_device_pm(const rf_comparator* c, int device, const uint64_t** d_out);                      // rf_api.hip
 RF_LOCAL std::vector<TileDesc> tiles_by_origin(const std::vector<TileDesc>& tiles, uint32_t n_exact, const uint32_t* orig);  // rf_api.hip
 RF_LOCAL rf_status plan(const rf_comparator* c, const rf_corpus* corpus, rf_op op, const rf_args* args, bool f64_out, ScanParams* p, RawKind* raw);  // rf_api_scan.hip
-RF_LOCAL rf_status refused_by_plan(const rf_comparator* c, const rf_corpus* corpus, rf_op op, const rf_args* args, bool f64_out);  // rf_api_scan.hip
+RF_LOCAL rf_status plan_multi(const MultiAsk& ask, const rf_comparator* const* cs, uint32_t q, const rf_corpus* corpus, rf_op op, const rf_args* args, MultiPlan* out);  // rf_api_topk_multi.hip
+RF_LOCAL rf_status check_multi_members(const char* fn, bool f64, const char* usize_only, const rf_comparator* const* cs, uint32_t q, rf_op op);  // rf_api_topk_multi.hip
 RF_LOCAL const uint32_t* corpus_head6_plane(const rf_corpus* corpus, hipStream_t st);                                  // rf_api_scan.hip
 RF_LOCAL const uint32_t* corpus_data6(const rf_corpus* corpus, hipStream_t st);                                        // rf_api_scan.hip
 RF_LOCAL const uint8_t* corpus_head8_plane(const rf_corpus* corpus, const ScanParams& p, RawKind raw, hipStream_t st);    // rf_api_scan.hip

@@ -24,6 +24,12 @@
 namespace rf {
 
 constexpr uint32_t kNormKeyMaxMaximum = 65535;  // the largest maximum the key is exact for
+// May a scan of a query of len1 symbols over candidates of up to max_len order by the key?  Its maximum is fin_mS * (len1 + len2) + fin_mM * max(len1, len2)
+// (rf_device.hpp "Finishing") and grows with the candidate's length, so the longest candidate decides.
+RF_NK_HD bool norm_key_fits(int32_t fin_mS, int32_t fin_mM, uint64_t len1, uint64_t max_len)
+{
+    return (uint64_t)fin_mS * (len1 + max_len) + (uint64_t)fin_mM * (len1 > max_len ? len1 : max_len) <= kNormKeyMaxMaximum;
+}
 
 // The computation: x = dist * 2^32 / maximum from ONE f64 multiply with scale = 2^32 / maximum (a division per maximum, not per
 // candidate: the kernel's maximum is tile-uniform), then one multiply-compare step.  The product is within 2^-20 of x (two roundings of

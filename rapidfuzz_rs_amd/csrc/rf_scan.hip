@@ -842,14 +842,9 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) __attribute__((amdgpu_waves_
 template <class State, int Q, bool kUniform>
 __global__ __launch_bounds__(kWave* kWavesPerBlock) void scan_multi_kernel(const ScanParams p)
 {
-    using Word = typename State::Word;
     static_assert(State::kWords == 1, "multi-query kernels are single-word");
-    __shared__ Word lds_pm[Q][256];
-    for (int i = threadIdx.x; i < Q * 256; i += kWave * kWavesPerBlock) {
-        const int q = i / 256, c = i % 256;
-        lds_pm[q][p.sigma[c]] = (Word)p.multi_pm[q][c];  // single-word tables: row stride 1
-    }
-    __syncthreads();
+    __shared__ typename State::Word lds_pm[Q][256];
+    fill_multi_tables(lds_pm, p);
 
     const uint32_t lane = threadIdx.x & (kWave - 1);
     const uint32_t wave = uniform(threadIdx.x / kWave);
@@ -902,33 +897,15 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void scan_multi_kernel(const
     }
 }
 
-template <class State, int Q>
-static hipError_t launch_multi_q(const ScanParams& p, hipStream_t stream, int grid)
-{
-    const dim3 g(grid), b(kWave * kWavesPerBlock);
-    if (p.tiles)
-        hipLaunchKernelGGL((scan_multi_kernel<State, Q, false>), g, b, 0, stream, p);
-    else
-        hipLaunchKernelGGL((scan_multi_kernel<State, Q, true>), g, b, 0, stream, p);
-    return hipGetLastError();
-}
-template <class State>
-static hipError_t launch_multi_state(const ScanParams& p, hipStream_t stream, int grid)
-{
-    switch (p.multi_q) {
-    case 2: return launch_multi_q<State, 2>(p, stream, grid);
-    case 4: return launch_multi_q<State, 4>(p, stream, grid);
-    default: return hipErrorInvalidValue;
-    }
-}
 // raw: RAW_LEV or RAW_LCS; all queries single-word; `narrow` = every query <= 32 symbols
 hipError_t launch_scan_multi(RawKind raw, bool narrow, const ScanParams& p, hipStream_t stream)
 {
     if (p.n_tiles == 0) return hipSuccess;
-    const int grid = scan_grid_full(p.n_tiles);
-    if (raw == RAW_LEV) return narrow ? launch_multi_state<Lev32State>(p, stream, grid) : launch_multi_state<LevState<1>>(p, stream, grid);
-    if (raw == RAW_LCS) return narrow ? launch_multi_state<Lcs32State>(p, stream, grid) : launch_multi_state<LcsState<1>>(p, stream, grid);
-    return hipErrorInvalidValue;
+    const dim3 g(scan_grid_full(p.n_tiles)), b(kWave * kWavesPerBlock);
+    return dispatch_multi(raw, narrow, p, [&](auto state, auto q, auto uniform) {
+        hipLaunchKernelGGL((scan_multi_kernel<typename decltype(state)::type, decltype(q)::value, decltype(uniform)::value>), g, b, 0, stream, p);
+        return hipGetLastError();
+    });
 }
 
 // Stand-alone selection (the post-all-gather merge, rf_topk_merge_keys_device): `count` keys -> the k smallest, ascending,

@@ -41,16 +41,11 @@ __device__ __forceinline__ void topk_multi_refresh_bound(const uint64_t* bound, 
 template <class State, int Q, bool kUniform, bool kNorm>
 __global__ __launch_bounds__(kWave* kWavesPerBlock) void topk_multi_kernel(const TopkMultiParams tp)
 {
-    using Word = typename State::Word;
     static_assert(State::kWords == 1, "multi-query kernels are single-word");
     const ScanParams& p = tp.s;
-    __shared__ Word lds_pm[Q][256];
+    __shared__ typename State::Word lds_pm[Q][256];
     __shared__ uint64_t lds_topk[kWavesPerBlock][kWave];
-    for (int i = threadIdx.x; i < Q * 256; i += kWave * kWavesPerBlock) {
-        const int q = i / 256, c = i % 256;
-        lds_pm[q][p.sigma[c]] = (Word)p.multi_pm[q][c];  // single-word tables: row stride 1
-    }
-    __syncthreads();
+    fill_multi_tables(lds_pm, p);
 
     const uint32_t lane = threadIdx.x & (kWave - 1);
     const uint32_t wave = uniform(threadIdx.x / kWave);
@@ -108,16 +103,13 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void topk_multi_kernel(const
                     const uint32_t v = usize_value(p, raw, len2, &keep, p.multi_len1[q]);  // emit_usize's arithmetic; None is not offered
                     mine = ((uint64_t)(p.topk_desc ? ~v : v) << 32) | idx;
                 } else {
-                    const TileFin f = tile_fin(p, p.multi_len1[q], len2);
-                    const uint32_t fmax = uniform(f.max);
-                    const double scale = norm_key_scale(fmax);
-                    const uint32_t dist = f.d0 + (uint32_t)p.fin_dR * raw;
+                    TileFin f = tile_fin(p, p.multi_len1[q], len2);
+                    f.max = uniform(f.max);
+                    const double scale = norm_key_scale(f.max);
+                    const uint32_t dist = fin_dist(p, f, raw);
                     keep = true;
-                    if (p.has_cutoff) {  // emit_fin's f64 branch, to the letter
-                        const double nd = fmax == 0 ? 0.0 : (double)dist / (double)fmax;
-                        keep = p.op == RF_OP_NORMALIZED_DISTANCE ? nd <= p.cutoff_f64 : (1.0 - nd) >= p.cutoff_f64;
-                    }
-                    mine = ((uint64_t)norm_key_scaled(dist, fmax, scale) << 32) | idx;
+                    if (p.has_cutoff) keep = norm_keep(p, norm_of(dist, f.max));  // (norm_dist's two halves: the division is paid under a cutoff only)
+                    mine = ((uint64_t)norm_key_scaled(dist, f.max, scale) << 32) | idx;
                 }
                 if (best[q].offer(mine, valid && keep, k, lane, limit[q])) topk_multi_list_changed(tp.bound + q * kTopkMultiLine64, best[q], k, lane, limit[q]);
             }
@@ -146,17 +138,10 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void topk_multi_kernel(const
                     if (x >= best[q].worst(k)) break;
                     best[q].insert(x, lane);
                 }
-            const bool pub = lane < k && best[q].key != ~0ull && best[q].key <= limit[q];
-            const uint64_t m = __ballot(pub);
-            if (m) {
-                uint32_t base = 0;
-                if (lane == 0) base = atomicAdd(tp.count + q * kTopkMultiLine32, (uint32_t)__popcll(m));
-                base = uniform(base);
-                const uint32_t at = base + (uint32_t)__popcll(m & ((1ull << lane) - 1));
-                // at < seg_cap always: the launcher sizes a segment for gridDim.x * k keys and a workgroup adds at most k (the test only keeps a
-                // launch with a wrong seg_cap inside its buffer)
-                if (pub && at < tp.seg_cap) tp.cand[(size_t)q * tp.seg_cap + at] = best[q].key;
-            }
+            // (a place is below seg_cap always: the launcher sizes a segment for gridDim.x * k keys and a workgroup adds at most k; the test only keeps a
+            // launch with a wrong seg_cap inside its buffer)
+            append_passers(tp.count + q * kTopkMultiLine32, tp.cand + (size_t)q * tp.seg_cap, tp.seg_cap, lane < k && best[q].key != ~0ull && best[q].key <= limit[q], lane,
+                           [&] { return best[q].key; });
         }
     }
 }
@@ -184,31 +169,6 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void topk_multi_select_kerne
     if (threadIdx.x == 0) tp.count[q * kTopkMultiLine32] = 0;
 }
 
-template <class State, int Q>
-static hipError_t launch_topk_multi_q(const TopkMultiParams& tp, hipStream_t stream, int grid)
-{
-    const dim3 g(grid), b(kWave * kWavesPerBlock);
-    if (tp.norm) {
-        if (tp.s.tiles)
-            hipLaunchKernelGGL((topk_multi_kernel<State, Q, false, true>), g, b, 0, stream, tp);
-        else
-            hipLaunchKernelGGL((topk_multi_kernel<State, Q, true, true>), g, b, 0, stream, tp);
-    } else if (tp.s.tiles)
-        hipLaunchKernelGGL((topk_multi_kernel<State, Q, false, false>), g, b, 0, stream, tp);
-    else
-        hipLaunchKernelGGL((topk_multi_kernel<State, Q, true, false>), g, b, 0, stream, tp);
-    return hipGetLastError();
-}
-template <class State>
-static hipError_t launch_topk_multi_state(const TopkMultiParams& tp, hipStream_t stream, int grid)
-{
-    switch (tp.s.multi_q) {
-    case 2: return launch_topk_multi_q<State, 2>(tp, stream, grid);
-    case 4: return launch_topk_multi_q<State, 4>(tp, stream, grid);
-    default: return hipErrorInvalidValue;
-    }
-}
-
 // The grid of a launch that visits `tiles` tiles: scan_grid(), i.e. at most RF_SCAN_BLOCKS_PER_CU (32) workgroups per CU -- 8192 on a whole MI355X.  With
 // it the worst case of a segment is 8192 x 64 keys = 4 MiB per query, 16 MiB for a group of four (the full scans' 256 per CU would make that 128 MiB).
 // What the cap costs (profiles/topk_multi_grid.txt, 16 queries over 100 M x 64, 32 / 64 / 128 workgroups per CU in one session): 64-bit Levenshtein
@@ -225,9 +185,15 @@ hipError_t launch_topk_multi(RawKind raw, bool narrow, const TopkMultiParams& tp
     if (span == 0) return hipSuccess;
     const int grid = topk_multi_grid((span + p.tile_step - 1) / p.tile_step);
     if ((uint64_t)grid * p.topk_k > tp.seg_cap) return hipErrorInvalidValue;
-    if (raw == RAW_LEV) return narrow ? launch_topk_multi_state<Lev32State>(tp, stream, grid) : launch_topk_multi_state<LevState<1>>(tp, stream, grid);
-    if (raw == RAW_LCS) return narrow ? launch_topk_multi_state<Lcs32State>(tp, stream, grid) : launch_topk_multi_state<LcsState<1>>(tp, stream, grid);
-    return hipErrorInvalidValue;
+    const dim3 g(grid), b(kWave * kWavesPerBlock);
+    return dispatch_multi(raw, narrow, p, [&](auto state, auto q, auto uniform) {
+        using State = typename decltype(state)::type;
+        if (tp.norm)
+            hipLaunchKernelGGL((topk_multi_kernel<State, decltype(q)::value, decltype(uniform)::value, true>), g, b, 0, stream, tp);
+        else
+            hipLaunchKernelGGL((topk_multi_kernel<State, decltype(q)::value, decltype(uniform)::value, false>), g, b, 0, stream, tp);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_topk_multi_select(const TopkMultiParams& tp, uint64_t* keys, hipStream_t stream)
