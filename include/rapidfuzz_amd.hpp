@@ -66,6 +66,21 @@ public:
     {
         check(rf_corpus_pack_rows_device(d_rows, n, len, stride, device, stream, &h_));
     }
+    /// ragged candidates already in device memory: candidate i = d_bytes[d_offsets[i] .. d_offsets[i + 1]) (n + 1 offsets, on the device too; n_elems
+    /// bytes are readable at d_bytes).  The corpus the string_view constructor builds from the same arrays on the host.
+    static Corpus from_device_ragged(const uint8_t* d_bytes, uint64_t n_elems, const uint64_t* d_offsets, size_t n, int device = 0, void* stream = nullptr)
+    {
+        Corpus c;
+        check(rf_corpus_pack_device(d_bytes, n_elems, d_offsets, n, device, stream, &c.h_));
+        return c;
+    }
+    /// the same over code points (u32 elements): the corpus the u32string_view constructor builds
+    static Corpus from_device_ragged(const uint32_t* d_elems, uint64_t n_elems, const uint64_t* d_offsets, size_t n, int device = 0, void* stream = nullptr)
+    {
+        Corpus c;
+        check(rf_corpus_pack_u32_device(d_elems, n_elems, d_offsets, n, device, stream, &c.h_));
+        return c;
+    }
     Corpus(const Corpus&) = delete;
     Corpus& operator=(const Corpus&) = delete;
     Corpus(Corpus&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }

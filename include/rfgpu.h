@@ -91,7 +91,9 @@
  *   RF_DEVICE_PACK_MIN            65536     fewest candidates for which rf_corpus_pack does its per-candidate work on the device (upload of the raw bytes + offsets, length
  *                                           histogram, stable radix sort by length, one scatter kernel per destination tile: rf_pack_ragged.hip) instead of the host's
  *                                           counting sort + byte scatter + one upload of the packed image; 0: always the host packer.  The same layout either way, byte
- *                                           for byte (rf_corpus_layout_host is the specification; candidates beyond 65535 symbols always take the host packer)
+ *                                           for byte (rf_corpus_layout_host is the specification; candidates beyond 65535 symbols always take the host packer).
+ *                                           rf_corpus_pack_u32 follows the same rule (rf_pack_wide.hip in front: symbol histogram, id image, raw stream);
+ *                                           rf_corpus_pack_device / rf_corpus_pack_u32_device do not read it: their input is on the device already
  *   RF_HINT_MIN_TILES             1024      fewest tiles of a corpus for which a per-candidate Levenshtein scan of a query beyond 64 symbols honours
  *                                           score_hint (pass under max(hint, 31), then only what it left unresolved: rf_hint.hip); 4294967295: never
  *   RF_HINT_SAMPLE_MIN_TILES      16384     fewest tiles for which such a call first runs the hint pass over every (tiles / 512)-th tile and drops the hint when fewer
@@ -285,10 +287,17 @@ const uint64_t *rf_comparator_pm(const rf_comparator *c, size_t *block_count);
  * rf_corpus_pack: ragged host input, candidate i = bytes[offsets[i] .. offsets[i+1]) (n+1 offsets).  From 65536 candidates on the input is uploaded as it is
  *   and length-bucketed on the device (100 M candidates of <= 64 symbols: host arrays to a scannable corpus in a fraction of a second, profiles/pack_r06.txt).
  * rf_corpus_pack_rows_device: n rows of `len` bytes already in device memory at d_rows + i*stride.
+ * rf_corpus_pack_device: ragged input already in device memory -- d_bytes (n_elems bytes readable) and the n+1 offsets d_offsets, both on `device`; the offsets
+ *   need not start at 0.  The corpus is the one rf_corpus_pack builds from the same arrays on the host (rf_corpus_save writes the same file), without the trip
+ *   home and back: lengths, sort and scatter read the caller's buffers in place, and nothing at or beyond d_bytes + n_elems is ever read.  Any n >= 1 takes the
+ *   device road (RF_DEVICE_PACK_MIN is about host input); a corpus with a candidate beyond 65535 symbols, or one whose temporaries do not fit, is copied home
+ *   and packed by the host packer.  The call orders itself after `stream` and is synchronous.  RF_ERR_INVALID_ARG: a null out, null offsets with n > 0, a null
+ *   payload with n_elems > 0 (these three before a device is touched), decreasing offsets, d_offsets[n] > n_elems.
  * Inputs are borrowed for the duration of the call only.  n < 2^32 - 1 per corpus. */
 rf_status rf_corpus_pack(const uint8_t *bytes, const uint64_t *offsets, size_t n, int device, rf_corpus **out);
 rf_status rf_corpus_pack_rows_device(const void *d_rows, size_t n, size_t len, size_t stride, int device,
                                      void *stream, rf_corpus **out);
+rf_status rf_corpus_pack_device(const uint8_t *d_bytes, uint64_t n_elems, const uint64_t *d_offsets, size_t n, int device, void *stream, rf_corpus **out);
 void rf_corpus_free(rf_corpus *c);
 /* The same layout computed on the host only (no device needed): for tools and for the CPU-side tests of the
  * packer.  Arrays are malloc'ed; release with rf_host_layout_free. */
@@ -336,8 +345,18 @@ rf_status rf_corpus_slot_index(const rf_corpus *c, uint32_t *out, rf_mem out_mem
  * Query symbols the corpus does not store share one never-matching id; refused with RF_ERR_UNSUPPORTED only: such a
  * query with more than 254 distinct symbols that the corpus DOES store (8-bit ids cannot tell them apart).
  * rf_corpus_alphabet_size: symbols with an id of their own (256 for a byte corpus), and how many share the
- * overflow id. */
+ * overflow id.
+ * From RF_DEVICE_PACK_MIN candidates on (65536; the rule of rf_corpus_pack) the elements and offsets are uploaded as they are and the symbol histogram, the id
+ * image and the raw stream are made on the device (rf_pack_wide.hip) in front of the byte corpus' own device packer; the alphabet is still chosen on the host,
+ * from exact counts, and the corpus saves to the same file either way.
+ * rf_corpus_pack_u32_device: the same from u32 elements and offsets already in device memory; arguments, errors and fall-backs as rf_corpus_pack_device, and a
+ * 0xFFFFFFFF element is RF_ERR_INVALID_ARG.
+ * A window: both u32 packers choose the alphabet from ALL of elems[0 .. offsets[n]), not only from [offsets[0], offsets[n]).  When the offsets start above 0 the
+ * elements in front of the first candidate are read and counted too: they take part in the ranking (and can take ids or push corpus symbols into the overflow
+ * class), and a 0xFFFFFFFF among them is refused.  Results stay exact either way; a caller that windows into a large buffer and wants neither the cost nor the
+ * foreign symbols passes the pointer advanced to the window and offsets rebased to start at 0. */
 rf_status rf_corpus_pack_u32(const uint32_t *elems, const uint64_t *offsets, size_t n, int device, rf_corpus **out);
+rf_status rf_corpus_pack_u32_device(const uint32_t *d_elems, uint64_t n_elems, const uint64_t *d_offsets, size_t n, int device, void *stream, rf_corpus **out);
 size_t rf_corpus_alphabet_size(const rf_corpus *c, size_t *overflow_symbols);
 
 /* ---- candidates read back out of the packed corpus ----------------------------------------------------

@@ -243,6 +243,27 @@ class Corpus:
         N.check(N.lib().rf_corpus_pack_rows_device(rows.data_ptr(), rows.shape[0], rows.shape[1], rows.stride(0) if rows.shape[0] > 1 else max(rows.shape[1], 1), dev, st, C.byref(h)))
         return cls(h.value, dev)
 
+    @classmethod
+    def from_device_ragged(cls, data, offsets, stream: Optional[int] = None) -> "Corpus":
+        """Ragged candidates already in device memory: `data` a 1-D contiguous torch CUDA tensor, `offsets` the n + 1 offsets (int64 or uint64) on the
+        same device; candidate i is data[offsets[i]:offsets[i + 1]] and the offsets need not start at 0.  uint8 data gives a byte corpus
+        (rf_corpus_pack_device), int32 or uint32 data a `char` corpus (rf_corpus_pack_u32_device): the corpus `from_ragged` / `from_ragged_u32` build
+        from the same arrays on the host, without the copy home and back."""
+        import torch
+
+        wide_types = [torch.int32] + ([torch.uint32] if hasattr(torch, "uint32") else [])
+        off_types = [torch.int64] + ([torch.uint64] if hasattr(torch, "uint64") else [])
+        if not (data.is_cuda and data.dim() == 1 and data.is_contiguous() and data.dtype in [torch.uint8] + wide_types):
+            raise ValueError("data must be a 1-D contiguous CUDA tensor of uint8, int32 or uint32")
+        if not (offsets.is_cuda and offsets.device == data.device and offsets.dim() == 1 and offsets.is_contiguous() and offsets.dtype in off_types and offsets.numel() >= 1):
+            raise ValueError("offsets must be a 1-D contiguous int64 or uint64 tensor of n + 1 entries on the device of data")
+        dev = data.device.index if data.device.index is not None else torch.cuda.current_device()
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        fn = N.lib().rf_corpus_pack_device if data.dtype == torch.uint8 else N.lib().rf_corpus_pack_u32_device
+        h = C.c_void_p()
+        N.check(fn(data.data_ptr() if data.numel() else None, data.numel(), offsets.data_ptr(), offsets.numel() - 1, dev, st, C.byref(h)))
+        return cls(h.value, dev)
+
 
 def host_layout(data: np.ndarray, offsets: np.ndarray) -> dict:
     """The packed layout computed on the host only (no GPU): for the packer's CPU tests."""

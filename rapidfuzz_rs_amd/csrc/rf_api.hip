@@ -6,6 +6,7 @@
 // into kernel parameters.  No metric is ever evaluated on the host: a shape without a device kernel is
 // RF_ERR_UNSUPPORTED.  Product code: never includes or links anything from oracle/.
 #include "rf_host.hpp"
+#include "rf_alphabet.hpp"
 
 namespace rf {
 
@@ -849,48 +850,45 @@ struct DeviceTemps {  // released on every way out
 
 }  // namespace
 
-// *declined = true: this corpus is the host packer's (too small to pay for the launches, a candidate beyond 65535 symbols, no room for the temporaries)
-static rf_status pack_ragged_device(const uint8_t* bytes, const uint64_t* offsets, size_t n, int device, rf_corpus** out, bool* declined)
+static bool soft_failure(hipError_t e)  // a temporary that cannot be had: the host packer's corpus, not an error
+{
+    if (e == hipSuccess) return false;
+    (void)hipGetLastError();
+    return true;
+}
+
+// What steps 2-7 pack: candidate i = d_bytes[d_off[i] - base .. d_off[i + 1] - base), first / total = d_off[0] / d_off[n] (already home, first <= total), `limit` bytes
+// readable at d_bytes.  The library's own upload buffers start at `first` and carry 16 bytes of padding; a caller's buffer starts at 0 and ends where it ends.
+struct DeviceInput {
+    const uint8_t* d_bytes;
+    uint64_t base, limit;
+    const uint64_t* d_off;
+    uint64_t first, total;
+};
+
+// Pack from device bytes + device offsets: what every road shares (host bytes, host u32 through the id image, and the two device-input entry points).  The caller
+// holds the DeviceGuard and owns `tmp`.  *declined = true: this corpus is the host packer's (a candidate beyond 65535 symbols, no room for the temporaries).
+static rf_status pack_from_device(const char* who, const DeviceInput& in, size_t n, int device, DeviceTemps& tmp, PhaseTimer& timer, rf_corpus** out, bool* declined)
 {
     *declined = true;
-    static const size_t min_n = (size_t)env_int("RF_DEVICE_PACK_MIN", 65536);  // 0: never
     constexpr uint32_t kMaxLen = 0xFFFFu;
-    if (!min_n || n < min_n || n >= 0x7FFFFFFFull || !offsets) return RF_OK;
-    const uint64_t first = offsets[0], total = offsets[n];
-    if (total < first || (total > first && !bytes)) return RF_OK;  // (the host packer words the error)
-    PhaseTimer timer;
-    DeviceGuard guard(device);
-    if (!guard.ok) {
-        set_error("rf_corpus_pack: cannot select device");
-        return RF_ERR_NO_DEVICE;
-    }
-    DeviceTemps tmp;
-    auto soft = [&](hipError_t e) {  // a temporary that cannot be had: the host packer, not an error
-        if (e == hipSuccess) return false;
-        (void)hipGetLastError();
-        return true;
-    };
-    uint8_t* d_bytes = nullptr;
-    uint64_t* d_off = nullptr;
+    if (n == 0 || n >= 0x7FFFFFFFull) return RF_OK;
+    const uint8_t* d_bytes = in.d_bytes;
+    const uint64_t* d_off = in.d_off;
+    const uint64_t first = in.first, total = in.total;
+    auto soft = soft_failure;
     uint32_t *d_keys = nullptr, *d_vals = nullptr, *d_keys2 = nullptr, *d_vals2 = nullptr, *d_status = nullptr;
     unsigned long long *d_counts = nullptr, *d_hist = nullptr;
-    if (soft(tmp.get((void**)&d_bytes, total - first + 16)) || soft(tmp.get((void**)&d_off, (n + 1) * sizeof(uint64_t))) || soft(tmp.get((void**)&d_keys, n * 4)) ||
-        soft(tmp.get((void**)&d_vals, n * 4)) || soft(tmp.get((void**)&d_keys2, n * 4)) || soft(tmp.get((void**)&d_vals2, n * 4)) ||
+    if (soft(tmp.get((void**)&d_keys, n * 4)) || soft(tmp.get((void**)&d_vals, n * 4)) || soft(tmp.get((void**)&d_keys2, n * 4)) || soft(tmp.get((void**)&d_vals2, n * 4)) ||
         soft(tmp.get((void**)&d_counts, ((size_t)kMaxLen + 1) * 8)) || soft(tmp.get((void**)&d_hist, 256 * 8)) || soft(tmp.get((void**)&d_status, 8)))
         return RF_OK;
     RF_HIP(hipMemsetAsync(d_counts, 0, ((size_t)kMaxLen + 1) * 8, nullptr));
     RF_HIP(hipMemsetAsync(d_hist, 0, 256 * 8, nullptr));
     RF_HIP(hipMemsetAsync(d_status, 0, 8, nullptr));
-    RF_HIP(hipMemsetAsync(d_bytes + (total - first), 0, 16, nullptr));
-    RF_HIP(hipStreamSynchronize(nullptr));
-    // ---- 1. the input, as it is
-    RF_HIP(staged_upload(d_off, offsets, (n + 1) * sizeof(uint64_t)));
-    RF_HIP(staged_upload(d_bytes, bytes + first, total - first));
-    timer.lap("device: upload bytes+offsets");
     // ---- 2. lengths (sort keys), their histogram, validation; the byte sample behind the symbol renaming
     RF_HIP(launch_ragged_lengths(d_off, (uint32_t)n, kMaxLen, d_keys, d_vals, d_counts, d_status, nullptr));
     const uint64_t span = total - first, block = 1u << 16, stride = std::max<uint64_t>(1, span / (256ull << 20));
-    RF_HIP(launch_ragged_byte_hist(d_bytes, 0, span, stride, d_hist, nullptr));
+    RF_HIP(launch_ragged_byte_hist(d_bytes, first - in.base, total - in.base, stride, d_hist, nullptr));
     std::vector<unsigned long long> counts((size_t)kMaxLen + 1);
     uint64_t hist[256];
     uint32_t status[2] = {0, 0};
@@ -898,7 +896,7 @@ static rf_status pack_ragged_device(const uint8_t* bytes, const uint64_t* offset
     RF_HIP(hipMemcpyAsync(hist, d_hist, sizeof(hist), hipMemcpyDeviceToHost, nullptr));
     RF_HIP(hipStreamSynchronize(nullptr));
     if (status[1] & 1u) {
-        set_error("rf_corpus_pack: offsets must be non-decreasing and candidates shorter than 4 GiB");
+        set_error(std::string(who) + ": offsets must be non-decreasing and candidates shorter than 4 GiB");
         *declined = false;
         return RF_ERR_INVALID_ARG;
     }
@@ -967,7 +965,7 @@ static rf_status pack_ragged_device(const uint8_t* bytes, const uint64_t* offset
         data_bytes += tile_bytes(hi);
     }
     if (slots >= 0xFFFFFFFFull || pool_n >= 0x80000000ull) {
-        set_error("rf_corpus_pack: too many candidates for one corpus");
+        set_error(std::string(who) + ": too many candidates for one corpus");
         *declined = false;
         return RF_ERR_INVALID_ARG;
     }
@@ -1046,12 +1044,12 @@ static rf_status pack_ragged_device(const uint8_t* bytes, const uint64_t* offset
         RF_HIP_C(hipMemcpyAsync(d_g + G, g_slot0.data(), groups.size() * 4, hipMemcpyHostToDevice, nullptr));
         RF_HIP_C(hipMemcpyAsync(d_g + 2 * G, g_in_exact.data(), groups.size() * 4, hipMemcpyHostToDevice, nullptr));
     }
-    RF_HIP_C(launch_ragged_scatter_tiles(d_bytes, first, d_off, d_vals2, identity ? nullptr : c->d_tiles, max_len, n_exact, d_by_len, d_g, d_g + G, d_g + 2 * G, c->d_sigma, c->d_data,
+    RF_HIP_C(launch_ragged_scatter_tiles(d_bytes, in.base, in.limit, d_off, d_vals2, identity ? nullptr : c->d_tiles, max_len, n_exact, d_by_len, d_g, d_g + G, d_g + 2 * G, c->d_sigma, c->d_data,
                                          c->d_orig, nullptr));
     if (c->n_mixed) {
         RF_HIP_C(hipMemcpyAsync(d_pool, pool_spos.data(), P * 4, hipMemcpyHostToDevice, nullptr));
         RF_HIP_C(hipMemcpyAsync(d_pool + P, pool_vslot0.data(), P * 4, hipMemcpyHostToDevice, nullptr));
-        RF_HIP_C(launch_ragged_scatter_mixed(d_bytes, first, d_off, d_vals2, c->d_mixed, c->n_mixed, (uint32_t)pool_n, c->d_mixed_len, d_pool, d_pool + P, c->d_sigma, c->d_data, c->d_orig,
+        RF_HIP_C(launch_ragged_scatter_mixed(d_bytes, in.base, in.limit, d_off, d_vals2, c->d_mixed, c->n_mixed, (uint32_t)pool_n, c->d_mixed_len, d_pool, d_pool + P, c->d_sigma, c->d_data, c->d_orig,
                                              c->d_mixed_orig, nullptr));
     }
     // ---- 7. the second tile order (tiles_by_origin): sorted on the device too (the host's std::sort of 1.5 M keys was most of what was left of the call)
@@ -1069,40 +1067,24 @@ static rf_status pack_ragged_device(const uint8_t* bytes, const uint64_t* offset
     return RF_OK;
 }
 
-rf_status rf_corpus_pack(const uint8_t* bytes, const uint64_t* offsets, size_t n, int device, rf_corpus** out)
-try {
-    if (!out) {
-        set_error("rf_corpus_pack: invalid argument");
-        return RF_ERR_INVALID_ARG;
-    }
-    {   // large inputs: the per-candidate work on the device (RF_DEVICE_PACK_MIN=<candidates>, default 65536; 0 = always the host packer)
-        bool declined = true;
-        const rf_status sd = pack_ragged_device(bytes, offsets, n, device, out, &declined);
-        if (!declined) return sd;
-    }
+// ---- the ragged packers: one host road each for bytes and u32 (the specification), and the device roads in front of them
+static rf_status pack_bytes_host(const uint8_t* bytes, const uint64_t* offsets, size_t n, int device, rf_corpus** out)
+{
     HostLayout L;
     const rf_status s = build_layout(bytes, offsets, n, &L);
     if (s != RF_OK) return s;
     return corpus_from_layout(L, n, device, out);
 }
-RF_ABI_CATCH
 
-// Candidates over `char` (or any u32) elements.  The corpus gets its own alphabet: the 254 most frequent symbols
+// Candidates over `char` (or any u32) elements.  The corpus gets its own alphabet (rf_alphabet.hpp): the 254 most frequent symbols
 // become byte ids 0..253 (frequency order, so the LDS rows the kernels touch most sit in distinct banks), every rarer
 // symbol becomes kOverflowId, and the id bytes are packed exactly like a byte corpus.  Results are exact for every
 // query that contains no overflow symbol (resolve()): candidate symbols outside the query only ever need to be
 // "not equal", and the lumped ones still are.
-rf_status rf_corpus_pack_u32(const uint32_t* elems, const uint64_t* offsets, size_t n, int device, rf_corpus** out)
-try {
-    if (!out || (n && !offsets)) {
-        set_error("rf_corpus_pack_u32: invalid argument");
-        return RF_ERR_INVALID_ARG;
-    }
+static_assert(kAlphabetIds == kOverflowId, "rf_alphabet.hpp hands out the ids below the overflow id");
+static rf_status pack_u32_host(const uint32_t* elems, const uint64_t* offsets, size_t n, int device, rf_corpus** out)
+{
     const uint64_t total = n ? offsets[n] : 0;
-    if (total && !elems) {
-        set_error("rf_corpus_pack_u32: null elements");
-        return RF_ERR_INVALID_ARG;
-    }
     // histogram: a direct table for the BMP, a hash map above it; one pair per worker thread, merged afterwards
     const size_t nthreads = total < (4u << 20) ? 1 : std::max<size_t>(1, std::min<size_t>(std::thread::hardware_concurrency(), 32));
     auto run = [&](auto&& fn) {  // fn(t): elements [total * t / nthreads, total * (t + 1) / nthreads)
@@ -1133,23 +1115,13 @@ try {
         for (uint32_t ch = 0; ch < 0x10000; ++ch) low[ch] += lows[t][ch];
         for (const auto& kv : highs[t]) high[kv.first] += kv.second;
     }
-    if (high.count(0xFFFFFFFFu)) {
+    AlphabetChoice choice;
+    if (!choose_alphabet(low.data(), std::vector<std::pair<uint32_t, uint64_t>>(high.begin(), high.end()), &choice)) {
         set_error("rf_corpus_pack_u32: the symbol 0xFFFFFFFF is reserved");
         return RF_ERR_INVALID_ARG;
     }
-    std::vector<std::pair<uint64_t, uint32_t>> syms;  // (count, symbol)
-    for (uint32_t ch = 0; ch < 0x10000; ++ch)
-        if (low[ch]) syms.emplace_back(low[ch], ch);
-    for (const auto& kv : high) syms.emplace_back(kv.second, kv.first);
-    std::sort(syms.begin(), syms.end(), [](const auto& a, const auto& b) { return a.first != b.first ? a.first > b.first : a.second < b.second; });
-    std::unordered_map<uint32_t, uint8_t> alphabet;
-    std::unordered_set<uint32_t> overflow;
-    for (size_t r = 0; r < syms.size(); ++r) {
-        if (r < (size_t)kOverflowId)
-            alphabet.emplace(syms[r].second, (uint8_t)r);
-        else
-            overflow.insert(syms[r].second);
-    }
+    std::unordered_map<uint32_t, uint8_t>& alphabet = choice.alphabet;
+    std::unordered_set<uint32_t>& overflow = choice.overflow;
     std::vector<uint16_t> low_id(0x10000, 0xFFFF);
     for (const auto& kv : alphabet)
         if (kv.first < 0x10000) low_id[kv.first] = kv.second;
@@ -1181,7 +1153,7 @@ try {
     if (!c->overflow.empty()) {
         // the symbol behind every packed byte, same chunk-interleaved positions (one worker per range of tiles); two bytes
         // per symbol when the whole corpus lies below 0xFFFF (the Basic Multilingual Plane), four otherwise
-        const bool narrow = high.empty() && low[0xFFFF] == 0;
+        const bool narrow = choice.narrow;
         c->raw_elem = narrow ? 2 : 4;
         const size_t raw_bytes = L.packed_size * c->raw_elem;
         std::unique_ptr<uint8_t[]> raw(new (std::nothrow) uint8_t[raw_bytes]);
@@ -1236,6 +1208,296 @@ try {
     }
     *out = c;
     return RF_OK;
+}
+
+static size_t device_pack_min()
+{
+    static const size_t min_n = (size_t)env_int("RF_DEVICE_PACK_MIN", 65536);  // 0: never
+    return min_n;
+}
+
+// rf_corpus_pack from host input, per-candidate work on the device.  *declined = true: this corpus is the host packer's (too small to pay for the launches, a
+// candidate beyond 65535 symbols, no room for the temporaries)
+static rf_status pack_ragged_device(const uint8_t* bytes, const uint64_t* offsets, size_t n, int device, rf_corpus** out, bool* declined)
+{
+    *declined = true;
+    const size_t min_n = device_pack_min();
+    if (!min_n || n < min_n || n >= 0x7FFFFFFFull || !offsets) return RF_OK;
+    const uint64_t first = offsets[0], total = offsets[n];
+    if (total < first || (total > first && !bytes)) return RF_OK;  // (the host packer words the error)
+    PhaseTimer timer;
+    DeviceGuard guard(device);
+    if (!guard.ok) {
+        set_error("rf_corpus_pack: cannot select device");
+        return RF_ERR_NO_DEVICE;
+    }
+    DeviceTemps tmp;
+    uint8_t* d_bytes = nullptr;
+    uint64_t* d_off = nullptr;
+    if (soft_failure(tmp.get((void**)&d_bytes, total - first + 16)) || soft_failure(tmp.get((void**)&d_off, (n + 1) * sizeof(uint64_t)))) return RF_OK;
+    RF_HIP(hipMemsetAsync(d_bytes + (total - first), 0, 16, nullptr));
+    RF_HIP(hipStreamSynchronize(nullptr));
+    // ---- 1. the input, as it is
+    RF_HIP(staged_upload(d_off, offsets, (n + 1) * sizeof(uint64_t)));
+    RF_HIP(staged_upload(d_bytes, bytes + first, total - first));
+    timer.lap("device: upload bytes+offsets");
+    const DeviceInput in{d_bytes, first, total - first + 16, d_off, first, total};
+    return pack_from_device("rf_corpus_pack", in, n, device, tmp, timer, out, declined);
+}
+
+// The u32 front end on the device (rf_pack_wide.hip): d_elems[0 .. total) are the elements the offsets index -- first <= total validated by the caller -- and d_off
+// the n + 1 offsets.  The alphabet is chosen from the counts of ALL of [0, total), as the host packer does it (a window whose offsets start above 0 counts what
+// lies in front of it too: the two roads must save the same file); ids and raw symbols are made for [first, total) only.
+// Exact symbol counts come home, the host picks the alphabet (rf_alphabet.hpp, as the host packer does), one pass writes the id image into a padded buffer of the
+// library's own, steps 2-7 pack it like any byte corpus, and a corpus with overflow symbols gets its raw stream by one more scatter.
+static rf_status pack_wide_from_device(const char* who, const uint32_t* d_elems, const uint64_t* d_off, uint64_t first, uint64_t total, size_t n, int device, DeviceTemps& tmp,
+                                       PhaseTimer& timer, rf_corpus** out, bool* declined)
+{
+    *declined = true;
+    const uint64_t span = total - first;
+    if (n == 0 || n >= 0x7FFFFFFFull || total >= (1ull << 40)) return RF_OK;
+    auto soft = soft_failure;
+    constexpr size_t kCounters = kLowSymbols + 3;  // the table, then: symbols above it, the compaction's cursor, flags
+    uint8_t *d_ids = nullptr, *d_table = nullptr, *d_hi_ids = nullptr;
+    uint32_t* d_hi_syms = nullptr;
+    unsigned long long* d_low = nullptr;
+    if (soft(tmp.get((void**)&d_ids, span + 16)) || soft(tmp.get((void**)&d_low, kCounters * 8)) || soft(tmp.get((void**)&d_table, kLowSymbols)) ||
+        soft(tmp.get((void**)&d_hi_syms, 256 * 4)) || soft(tmp.get((void**)&d_hi_ids, 256)))
+        return RF_OK;
+    RF_HIP(hipMemsetAsync(d_low, 0, kCounters * 8, nullptr));
+    RF_HIP(hipMemsetAsync(d_ids + span, 0, 16, nullptr));
+    // ---- a. exact symbol counts
+    RF_HIP(launch_wide_hist(d_elems, total, d_low, d_low + kLowSymbols, reinterpret_cast<uint32_t*>(d_low + kLowSymbols + 2), nullptr));
+    std::vector<uint64_t> low(kCounters);
+    RF_HIP(hipMemcpy(low.data(), d_low, kCounters * 8, hipMemcpyDeviceToHost));
+    if (low[kLowSymbols + 2] & 1u) {
+        set_error(std::string(who) + ": the symbol 0xFFFFFFFF is reserved");
+        *declined = false;
+        return RF_ERR_INVALID_ARG;
+    }
+    const uint64_t n_high = low[kLowSymbols];
+    if (n_high >= 0x7FFFFFFFull) return RF_OK;  // (hipcub counts items in an int)
+    std::vector<std::pair<uint32_t, uint64_t>> high;
+    if (n_high) {  // the symbols above the table: collected, sorted, run-length encoded
+        uint32_t *d_high = nullptr, *d_sorted = nullptr, *d_unique = nullptr, *d_runs = nullptr, *d_num_runs = nullptr;
+        void* d_temp = nullptr;
+        const size_t temp_bytes = wide_runs_temp_bytes((uint32_t)n_high);
+        if (soft(tmp.get((void**)&d_high, n_high * 4)) || soft(tmp.get((void**)&d_sorted, n_high * 4)) || soft(tmp.get((void**)&d_unique, n_high * 4)) ||
+            soft(tmp.get((void**)&d_runs, n_high * 4)) || soft(tmp.get((void**)&d_num_runs, 4)) || soft(tmp.get(&d_temp, temp_bytes)))
+            return RF_OK;
+        RF_HIP(launch_wide_compact_high(d_elems, total, d_high, (uint32_t)n_high, d_low + kLowSymbols + 1, nullptr));
+        RF_HIP(launch_wide_runs(d_high, d_sorted, (uint32_t)n_high, d_unique, d_runs, d_num_runs, d_temp, temp_bytes, nullptr));
+        uint32_t runs = 0;
+        RF_HIP(hipMemcpy(&runs, d_num_runs, 4, hipMemcpyDeviceToHost));
+        if (runs > n_high) runs = (uint32_t)n_high;
+        std::vector<uint32_t> syms(runs), counts(runs);
+        RF_HIP(hipMemcpy(syms.data(), d_unique, (size_t)runs * 4, hipMemcpyDeviceToHost));
+        RF_HIP(hipMemcpy(counts.data(), d_runs, (size_t)runs * 4, hipMemcpyDeviceToHost));
+        high.reserve(runs);
+        for (uint32_t r = 0; r < runs; ++r) high.emplace_back(syms[r], (uint64_t)counts[r]);
+    }
+    timer.lap("device: u32 symbol histogram");
+    // ---- b. the alphabet (host) and the id image
+    AlphabetChoice choice;
+    if (!choose_alphabet(low.data(), high, &choice)) {
+        set_error(std::string(who) + ": the symbol 0xFFFFFFFF is reserved");
+        *declined = false;
+        return RF_ERR_INVALID_ARG;
+    }
+    {
+        std::vector<uint8_t> table(kLowSymbols, kOverflowId), hi_ids;
+        std::vector<std::pair<uint32_t, uint8_t>> hi;
+        for (const auto& kv : choice.alphabet) {
+            if (kv.first < kLowSymbols)
+                table[kv.first] = kv.second;
+            else
+                hi.emplace_back(kv.first, kv.second);
+        }
+        std::sort(hi.begin(), hi.end());
+        std::vector<uint32_t> hi_syms;
+        for (const auto& kv : hi) hi_syms.push_back(kv.first), hi_ids.push_back(kv.second);
+        RF_HIP(hipMemcpy(d_table, table.data(), kLowSymbols, hipMemcpyHostToDevice));
+        if (!hi.empty()) {
+            RF_HIP(hipMemcpy(d_hi_syms, hi_syms.data(), hi_syms.size() * 4, hipMemcpyHostToDevice));
+            RF_HIP(hipMemcpy(d_hi_ids, hi_ids.data(), hi_ids.size(), hipMemcpyHostToDevice));
+        }
+        RF_HIP(launch_wide_ids(d_elems + first, span, d_table, d_hi_syms, d_hi_ids, (uint32_t)hi.size(), kOverflowId, d_ids, nullptr));
+        RF_HIP(hipStreamSynchronize(nullptr));
+    }
+    timer.lap("device: u32 alphabet + id image");
+    // ---- c. steps 2-7 over the id image
+    rf_corpus* c = nullptr;
+    const DeviceInput in{d_ids, first, span + 16, d_off, first, total};
+    const rf_status s = pack_from_device(who, in, n, device, tmp, timer, &c, declined);
+    if (*declined || s != RF_OK) return s;
+    c->wide = true;
+    c->alphabet = std::move(choice.alphabet);
+    c->overflow = std::move(choice.overflow);
+    if (!c->overflow.empty()) {  // ---- d. the symbol behind every packed byte, same positions; the padding value everywhere else
+        auto fail = [&](rf_status st) {
+            rf_corpus_free(c);
+            return st;
+        };
+        c->raw_elem = choice.narrow ? 2 : 4;
+        const size_t raw_bytes = (size_t)c->data_bytes * c->raw_elem;
+        RF_HIP_C(hipMalloc(&c->d_raw, raw_bytes));
+        c->device_bytes += raw_bytes;
+        RF_HIP_C(hipMemsetAsync(static_cast<uint8_t*>(c->d_raw) + (raw_bytes - kTailPad * c->raw_elem), 0xFF, kTailPad * c->raw_elem, nullptr));
+        RF_HIP_C(launch_wide_raw(d_elems + first, first, d_off, (uint32_t)n, c->uniform ? nullptr : c->d_tiles, c->uniform_len, c->n_exact, c->d_orig, c->d_mixed, c->n_mixed, c->d_mixed_len,
+                                 c->d_mixed_orig, c->d_raw, c->raw_elem, nullptr));
+        RF_HIP_C(hipStreamSynchronize(nullptr));
+        timer.lap("device: u32 raw stream");
+    }
+    *out = c;
+    return RF_OK;
+}
+
+// rf_corpus_pack_u32 from host input on the device road: the elements and offsets go up as they are
+static rf_status pack_wide_device(const uint32_t* elems, const uint64_t* offsets, size_t n, int device, rf_corpus** out, bool* declined)
+{
+    *declined = true;
+    const size_t min_n = device_pack_min();
+    if (!min_n || n < min_n || n >= 0x7FFFFFFFull) return RF_OK;
+    const uint64_t first = offsets[0], total = offsets[n];
+    if (total < first) return RF_OK;  // (the host packer words the error)
+    PhaseTimer timer;
+    DeviceGuard guard(device);
+    if (!guard.ok) {
+        set_error("rf_corpus_pack_u32: cannot select device");
+        return RF_ERR_NO_DEVICE;
+    }
+    DeviceTemps tmp;
+    uint32_t* d_elems = nullptr;
+    uint64_t* d_off = nullptr;
+    if (soft_failure(tmp.get((void**)&d_elems, total * 4)) || soft_failure(tmp.get((void**)&d_off, (n + 1) * sizeof(uint64_t)))) return RF_OK;
+    RF_HIP(staged_upload(d_off, offsets, (n + 1) * sizeof(uint64_t)));
+    RF_HIP(staged_upload(d_elems, elems, total * 4));
+    timer.lap("device: u32 upload elems+offsets");
+    return pack_wide_from_device("rf_corpus_pack_u32", d_elems, d_off, first, total, n, device, tmp, timer, out, declined);
+}
+
+// Device-resident input.  `elem` = 1 (bytes) or 4 (u32 symbols).  What the device road declines is copied home and given to the host packer.
+static rf_status pack_device_input(const char* who, const void* d_payload, uint32_t elem, uint64_t n_elems, const uint64_t* d_offsets, size_t n, int device, void* stream, rf_corpus** out)
+{
+    if (!out || (n && !d_offsets) || n >= 0xFFFFFFFFull) {
+        set_error(std::string(who) + ": invalid argument");
+        return RF_ERR_INVALID_ARG;
+    }
+    if (!d_payload && n_elems) {  // (a null payload is only good for candidates that are all empty)
+        set_error(std::string(who) + ": null payload");
+        return RF_ERR_INVALID_ARG;
+    }
+    rf_corpus* c = nullptr;
+    if (n == 0) {
+        const rf_status s = elem == 1 ? pack_bytes_host(nullptr, nullptr, 0, device, &c) : pack_u32_host(nullptr, nullptr, 0, device, &c);
+        if (s == RF_OK) *out = c;
+        return s;
+    }
+    DeviceGuard guard(device);
+    if (!guard.ok) {
+        set_error(std::string(who) + ": cannot select device");
+        return RF_ERR_NO_DEVICE;
+    }
+    RF_HIP(hipStreamSynchronize((hipStream_t)stream));  // the call orders itself after `stream`; from here on it works in the null stream and is synchronous
+    uint64_t first = 0, total = 0;
+    RF_HIP(hipMemcpy(&first, d_offsets, 8, hipMemcpyDeviceToHost));
+    RF_HIP(hipMemcpy(&total, d_offsets + n, 8, hipMemcpyDeviceToHost));
+    if (total < first) {
+        set_error(std::string(who) + ": offsets must be non-decreasing and candidates shorter than 4 GiB");
+        return RF_ERR_INVALID_ARG;
+    }
+    if (total > n_elems) {
+        set_error(std::string(who) + ": the offsets run beyond n_elems");
+        return RF_ERR_INVALID_ARG;
+    }
+    if (total > first && !d_payload) {
+        set_error(std::string(who) + ": null payload");
+        return RF_ERR_INVALID_ARG;
+    }
+    {
+        PhaseTimer timer;
+        DeviceTemps tmp;
+        bool declined = true;
+        rf_status s;
+        if (elem == 1) {
+            const DeviceInput in{static_cast<const uint8_t*>(d_payload), 0, n_elems, d_offsets, first, total};
+            s = pack_from_device(who, in, n, device, tmp, timer, &c, &declined);
+        } else {
+            s = pack_wide_from_device(who, static_cast<const uint32_t*>(d_payload), d_offsets, first, total, n, device, tmp, timer, &c, &declined);
+        }
+        if (!declined) {
+            if (s == RF_OK) *out = c;
+            return s;
+        }
+    }
+    // the host road: offsets and the span they cover come home (checked here: the host packer trusts its offsets)
+    std::vector<uint64_t> offsets(n + 1);
+    RF_HIP(hipMemcpy(offsets.data(), d_offsets, (n + 1) * 8, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i)
+        if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > 0xFFFFFFF0ull) {
+            set_error(std::string(who) + ": offsets must be non-decreasing and candidates shorter than 4 GiB");
+            return RF_ERR_INVALID_ARG;
+        }
+    if (offsets[n] > n_elems) {
+        set_error(std::string(who) + ": the offsets run beyond n_elems");
+        return RF_ERR_INVALID_ARG;
+    }
+    const uint64_t base = elem == 1 ? offsets[0] : 0, span = offsets[n] - base;  // (the u32 packer counts the symbols in front of a window too)
+    std::unique_ptr<uint8_t[]> home(new (std::nothrow) uint8_t[std::max<uint64_t>(1, span * elem)]);
+    if (!home) {
+        set_error(std::string(who) + ": out of host memory");
+        return RF_ERR_OOM;
+    }
+    if (span) RF_HIP(hipMemcpy(home.get(), static_cast<const uint8_t*>(d_payload) + base * elem, span * elem, hipMemcpyDeviceToHost));
+    for (uint64_t& o : offsets) o -= base;
+    const rf_status s = elem == 1 ? pack_bytes_host(home.get(), offsets.data(), n, device, &c) : pack_u32_host(reinterpret_cast<const uint32_t*>(home.get()), offsets.data(), n, device, &c);
+    if (s == RF_OK) *out = c;
+    return s;
+}
+
+rf_status rf_corpus_pack(const uint8_t* bytes, const uint64_t* offsets, size_t n, int device, rf_corpus** out)
+try {
+    if (!out) {
+        set_error("rf_corpus_pack: invalid argument");
+        return RF_ERR_INVALID_ARG;
+    }
+    {   // large inputs: the per-candidate work on the device (RF_DEVICE_PACK_MIN=<candidates>, default 65536; 0 = always the host packer)
+        bool declined = true;
+        const rf_status sd = pack_ragged_device(bytes, offsets, n, device, out, &declined);
+        if (!declined) return sd;
+    }
+    return pack_bytes_host(bytes, offsets, n, device, out);
+}
+RF_ABI_CATCH
+
+rf_status rf_corpus_pack_u32(const uint32_t* elems, const uint64_t* offsets, size_t n, int device, rf_corpus** out)
+try {
+    if (!out || (n && !offsets)) {
+        set_error("rf_corpus_pack_u32: invalid argument");
+        return RF_ERR_INVALID_ARG;
+    }
+    if (n && offsets[n] && !elems) {
+        set_error("rf_corpus_pack_u32: null elements");
+        return RF_ERR_INVALID_ARG;
+    }
+    {   // large inputs: histogram, id image and raw stream on the device, in front of the byte pipeline (the same RF_DEVICE_PACK_MIN)
+        bool declined = true;
+        const rf_status sd = pack_wide_device(elems, offsets, n, device, out, &declined);
+        if (!declined) return sd;
+    }
+    return pack_u32_host(elems, offsets, n, device, out);
+}
+RF_ABI_CATCH
+
+rf_status rf_corpus_pack_device(const uint8_t* d_bytes, uint64_t n_elems, const uint64_t* d_offsets, size_t n, int device, void* stream, rf_corpus** out)
+try {
+    return pack_device_input("rf_corpus_pack_device", d_bytes, 1, n_elems, d_offsets, n, device, stream, out);
+}
+RF_ABI_CATCH
+
+rf_status rf_corpus_pack_u32_device(const uint32_t* d_elems, uint64_t n_elems, const uint64_t* d_offsets, size_t n, int device, void* stream, rf_corpus** out)
+try {
+    return pack_device_input("rf_corpus_pack_u32_device", d_elems, 4, n_elems, d_offsets, n, device, stream, out);
 }
 RF_ABI_CATCH
 

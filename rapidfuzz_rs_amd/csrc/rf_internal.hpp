@@ -288,7 +288,7 @@ hipError_t launch_pack_rows(const uint8_t* rows, size_t n, uint32_t len, size_t 
                             uint32_t n_tiles, const uint8_t* sigma, hipStream_t stream);
 hipError_t launch_translate(const void* raw, uint32_t raw_elem, uint64_t n_bytes, const uint32_t* keys, const uint8_t* vals, uint32_t cap, uint8_t* out,
                             hipStream_t stream);
-// rf_pack_ragged.hip: the device half of rf_corpus_pack (ragged host input)
+// rf_pack_ragged.hip: the device half of rf_corpus_pack.  The scatters read bytes[offsets[i] - first ...) and never at or beyond bytes + limit
 hipError_t launch_ragged_lengths(const uint64_t* offsets, uint32_t n, uint32_t max_len_allowed, uint32_t* keys, uint32_t* vals, unsigned long long* counts, uint32_t* status,
                                  hipStream_t st);  // status[0] = longest length, status[1]: bit 0 = offsets decrease, bit 1 = a candidate longer than max_len_allowed
 hipError_t launch_ragged_byte_hist(const uint8_t* bytes, uint64_t first, uint64_t total, uint64_t stride, unsigned long long* hist, hipStream_t st);
@@ -297,12 +297,21 @@ hipError_t launch_tiles_by_origin(const uint32_t* orig, const TileDesc* tiles, u
                                   void* temp, size_t temp_bytes, TileDesc* out, hipStream_t st);
 hipError_t launch_ragged_sort(const uint32_t* keys_in, uint32_t* keys_out, const uint32_t* vals_in, uint32_t* vals_out, uint32_t n, uint32_t bits, void* temp, size_t temp_bytes,
                               hipStream_t st);
-hipError_t launch_ragged_scatter_tiles(const uint8_t* bytes, uint64_t first, const uint64_t* offsets, const uint32_t* sorted_idx, const TileDesc* tiles, uint32_t uniform_len, uint32_t n_exact,
+hipError_t launch_ragged_scatter_tiles(const uint8_t* bytes, uint64_t first, uint64_t limit, const uint64_t* offsets, const uint32_t* sorted_idx, const TileDesc* tiles, uint32_t uniform_len, uint32_t n_exact,
                                        const uint32_t* by_len, const uint32_t* g_start, const uint32_t* g_slot0, const uint32_t* g_in_exact, const uint8_t* sigma, uint8_t* packed,
                                        uint32_t* orig, hipStream_t st);
-hipError_t launch_ragged_scatter_mixed(const uint8_t* bytes, uint64_t first, const uint64_t* offsets, const uint32_t* sorted_idx, const MixedDesc* mixed, uint32_t n_mixed, uint32_t pool_n,
+hipError_t launch_ragged_scatter_mixed(const uint8_t* bytes, uint64_t first, uint64_t limit, const uint64_t* offsets, const uint32_t* sorted_idx, const MixedDesc* mixed, uint32_t n_mixed, uint32_t pool_n,
                                        const uint32_t* pool_len, const uint32_t* pool_spos, const uint32_t* pool_vslot0, const uint8_t* sigma, uint8_t* packed, uint32_t* orig,
                                        uint32_t* mixed_orig, hipStream_t st);
+// rf_pack_wide.hip: the device front end of rf_corpus_pack_u32 (elems[0 .. span) = the symbols of the corpus)
+hipError_t launch_wide_hist(const uint32_t* elems, uint64_t span, unsigned long long* low, unsigned long long* n_high, uint32_t* flags, hipStream_t st);  // span < 2^40
+hipError_t launch_wide_compact_high(const uint32_t* elems, uint64_t span, uint32_t* out, uint32_t cap, unsigned long long* cursor, hipStream_t st);
+size_t wide_runs_temp_bytes(uint32_t n);
+hipError_t launch_wide_runs(const uint32_t* syms, uint32_t* sorted, uint32_t n, uint32_t* unique, uint32_t* counts, uint32_t* num_runs, void* temp, size_t temp_bytes, hipStream_t st);
+hipError_t launch_wide_ids(const uint32_t* elems, uint64_t span, const uint8_t* table, const uint32_t* hi_syms, const uint8_t* hi_ids, uint32_t n_hi, uint32_t overflow_id, uint8_t* out,
+                           hipStream_t st);
+hipError_t launch_wide_raw(const uint32_t* elems, uint64_t first, const uint64_t* offsets, uint32_t n, const TileDesc* tiles, uint32_t uniform_len, uint32_t n_exact, const uint32_t* orig,
+                           const MixedDesc* mixed, uint32_t n_mixed, const uint32_t* mixed_len, const uint32_t* mixed_orig, void* raw, uint32_t raw_elem, hipStream_t st);
 int scan_max_grid();
 int list_max_grid(int per_cu);  // CUs x min(per_cu, RF_SCAN_BLOCKS_PER_CU): the grids of the launches that walk survivor lists
 // results of a ragged corpus in original order without scattered stores (rf_pack.hip): slot -> slot / candidate -> slot maps, and the gather

@@ -42,6 +42,25 @@ impl Corpus {
         check(unsafe { rf_corpus_pack_u32(elems.as_ptr(), offsets.as_ptr(), offsets.len() - 1, device, &mut h) })?;
         Ok(Corpus(h))
     }
+    /// Ragged byte candidates already in device memory: candidate i = `d_bytes[d_offsets[i] .. d_offsets[i + 1])`, `n + 1` offsets on the same device, `n_elems`
+    /// bytes readable at `d_bytes`; the call orders itself after `stream` and is synchronous (rfgpu.h rf_corpus_pack_device).
+    ///
+    /// # Safety
+    /// `d_bytes` and `d_offsets` must be device allocations of at least `n_elems` bytes and `n + 1` offsets on `device`.
+    pub unsafe fn from_device_ragged(d_bytes: *const u8, n_elems: u64, d_offsets: *const u64, n: usize, device: i32, stream: *mut std::ffi::c_void) -> Result<Self, Error> {
+        let mut h = std::ptr::null_mut();
+        check(rf_corpus_pack_device(d_bytes, n_elems, d_offsets, n, device, stream, &mut h))?;
+        Ok(Corpus(h))
+    }
+    /// The same over `char`s held as u32 elements in device memory (rfgpu.h rf_corpus_pack_u32_device): the corpus [`Corpus::from_chars`] builds on the host.
+    ///
+    /// # Safety
+    /// As [`Corpus::from_device_ragged`], with `n_elems` u32 elements readable at `d_elems`.
+    pub unsafe fn from_device_chars(d_elems: *const u32, n_elems: u64, d_offsets: *const u64, n: usize, device: i32, stream: *mut std::ffi::c_void) -> Result<Self, Error> {
+        let mut h = std::ptr::null_mut();
+        check(rf_corpus_pack_u32_device(d_elems, n_elems, d_offsets, n, device, stream, &mut h))?;
+        Ok(Corpus(h))
+    }
     /// A packed corpus written by [`Corpus::save`]; validated on load.
     pub fn load(path: &str, device: i32) -> Result<Self, Error> {
         let p = CString::new(path).map_err(|_| Error(RF_ERR_INVALID_ARG, "path contains NUL".into()))?;
