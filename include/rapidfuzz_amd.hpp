@@ -303,6 +303,25 @@ public:
         return filter_multi_f64(scorers, c, RF_OP_NORMALIZED_SIMILARITY, a.to_c(), order, index_base);
     }
 
+    // ---- all pairs of two packed corpora within the cutoff, one call (rf_join_u32): the triples (query row, candidate, score) -- what distance_filter_many of
+    // a comparator over row `query` of `queries` reports for `candidate` -- ascending by (position in query_indices, candidate) or, RF_JOIN_ANY, as they arrived.
+    // `queries` and `c` may be the same corpus (a self-join; `upper` then keeps each unordered pair once and no (i, i)).  query_indices: the rows to join, nullptr = every row (an empty list: no pair).  The
+    // cutoff is required.  usize metrics only.
+    struct JoinTriple {
+        uint64_t query, candidate;
+        size_t score;
+    };
+    static std::vector<JoinTriple> distance_join(const Corpus& queries, const Corpus& c, const Args<usize_result>& a, bool upper = false, rf_join_order order = RF_JOIN_BY_QUERY,
+                                                 const std::vector<uint64_t>* query_indices = nullptr, uint64_t query_base = 0, uint64_t index_base = 0)
+    {
+        return join(queries, c, RF_OP_DISTANCE, a.to_c(), upper, order, query_indices, query_base, index_base);
+    }
+    static std::vector<JoinTriple> similarity_join(const Corpus& queries, const Corpus& c, const Args<usize_result>& a, bool upper = false, rf_join_order order = RF_JOIN_BY_QUERY,
+                                                   const std::vector<uint64_t>* query_indices = nullptr, uint64_t query_base = 0, uint64_t index_base = 0)
+    {
+        return join(queries, c, RF_OP_SIMILARITY, a.to_c(), upper, order, query_indices, query_base, index_base);
+    }
+
     // ---- the reference's per-candidate methods (a one-candidate corpus through the same kernels)
     std::optional<usize_result> distance_with_args(std::string_view s2, const Args<usize_result>& a) const
     {
@@ -406,6 +425,26 @@ private:
                 for (uint64_t m = 0; m < count[j]; ++m) res[j].emplace_back(index[j * cap + m], (size_t)score[j * cap + m]);
             return res;
         }
+    }
+    static std::vector<JoinTriple> join(const Corpus& queries, const Corpus& c, rf_op op, const rf_args& a, bool upper, rf_join_order order,
+                                        const std::vector<uint64_t>* query_indices, uint64_t query_base, uint64_t index_base)
+    {
+        static_assert(!FloatMetric, "rf_join_u32 serves the usize-valued metrics");
+        if (query_indices && query_indices->empty()) return {};  // (an empty selection is no pair; only a null pointer asks for every row)
+        const uint64_t* qi = query_indices ? query_indices->data() : nullptr;
+        const uint64_t m = query_indices ? query_indices->size() : queries.size();
+        const uint32_t flags = upper ? RF_JOIN_UPPER : 0u;
+        uint64_t count = 0;  // (a pure count first: the call reports the true number of pairs)
+        check(rf_join_u32(M, queries.handle(), qi, m, c.handle(), op, &a, flags, query_base, index_base, 0, nullptr, nullptr, nullptr, &count, order, nullptr));
+        std::vector<JoinTriple> res;
+        if (count == 0) return res;
+        std::vector<uint64_t> query(count), index(count);
+        std::vector<uint32_t> score(count);
+        const uint64_t cap = count;
+        check(rf_join_u32(M, queries.handle(), qi, m, c.handle(), op, &a, flags, query_base, index_base, cap, query.data(), index.data(), score.data(), &count, order, nullptr));
+        res.reserve(std::min(cap, count));
+        for (uint64_t t = 0; t < std::min(cap, count); ++t) res.push_back(JoinTriple{query[t], index[t], (size_t)score[t]});
+        return res;
     }
     static std::vector<std::vector<std::pair<uint64_t, double>>> filter_multi_f64(const std::vector<const BatchComparator*>& scorers, const Corpus& c, rf_op op,
                                                                                   const rf_args& a, rf_filter_order order, uint64_t index_base)

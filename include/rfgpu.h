@@ -73,6 +73,8 @@
  *   RF_TOPK_MULTI                 1         0: rf_topk_multi_u32 / _f64 send every query through rf_topk_u32 / _f64 instead of fusing 4 (or 2) to a pass over the corpus
  *   RF_FILTER_MULTI               1         0: rf_filter_multi_u32 / _f64 send every query through rf_filter_u32 / _f64 instead of fusing tight-cutoff queries 4 (or 2) to a pass over the corpus
  *   RF_FILTER_MULTI_F64_ROUTE     1         0: rf_filter_multi_f64 fuses every fusable query, also the shapes its measured routing rules send through rf_filter_f64 (A/B measurements)
+ *   RF_JOIN                       1         0: rf_join_u32 sends every row of Q through rf_corpus_take + rf_filter_u32 instead of the device road (identical results)
+ *   RF_JOIN_BATCH                 16384     most rows of Q per device batch of rf_join_u32 (2 KiB of table scratch per row; 1 .. 1048576)
  *   RF_JARO_PRIV                  0         1: Jaro asm kernel gathers from a conflict-free copy of the pattern table (corpora of <= 64 symbols; measured: no gain)
  *   RF_WF_REG                     1         0: LDS rows instead of register rows for generalized weights, queries <= 64
  *   RF_TRANSLATE_DIRECT           1         0: staged translation of u32 overflow symbols
@@ -575,6 +577,44 @@ rf_status rf_filter_multi_f64(const rf_comparator *const *cs, uint32_t q, const 
                               const rf_args *args, uint64_t index_base, uint64_t capacity,
                               uint64_t *out_index, double *out_score, uint64_t *out_count,
                               rf_filter_order order, void *stream);
+
+/* ---- join: all pairs of two packed corpora within a cutoff --------------------------------------------
+ * "For every record, the records within k edits of it" (dedup, record linkage) with the queries themselves a packed corpus in HBM.
+ * Q = the rows query_indices[0 .. m) of `queries`, in any order, repeats allowed (a repeated row yields its pairs once per occurrence);
+ * query_indices == NULL asks for every row and m must then equal rf_corpus_count(queries).  The result is the multiset of triples
+ *   (query_base + qi, index_base + j, v)
+ * where v is what rf_filter_u32(rf_comparator_new(metric, the bytes of row qi), corpus, op, args, ...) returns for candidate j: the same
+ * values, the same None rule, the same documented deviations as the single-query call.  `queries` and `corpus` may be the same handle.
+ * op is RF_OP_DISTANCE or RF_OP_SIMILARITY.  args MUST carry a score_cutoff: without one the answer is all m x n pairs, and the call refuses
+ * that as RF_ERR_INVALID_ARG.  flags: RF_JOIN_UPPER keeps a pair only if candidate index > query index (both local, before the bases): a
+ * self-join then reports each unordered pair once and no (i, i).
+ * Outputs are HOST arrays, parallel, one entry per pair.  *out_count is ALWAYS the true number of pairs; when it exceeds `capacity` the
+ * arrays hold `capacity` valid, distinct, qualifying triples in the requested order among themselves.  capacity == 0 is a pure count (the
+ * arrays may then be NULL).  `capacity` is ALLOCATED as given -- 12 bytes per entry on the device (at most m x n entries) and 32 per entry on the
+ * host while the call runs -- so a caller who cannot bound the answer counts first (capacity 0) and then passes the count; a capacity the device
+ * cannot hold is RF_ERR_OOM, not a shorter answer.  A call that does not return RF_OK writes nothing.  order: RF_JOIN_BY_QUERY = ascending (position in Q,
+ * candidate index), RF_JOIN_ANY = arrival order.
+ * Two roads.  On the DEVICE: both corpora hold bytes, levenshtein (uniform or Indel-like weights) / indel / lcs_seq, rows of <= 64 symbols
+ * whose cutoff is TIGHT (the planner's early-out rule, as rf_filter_multi_u32).  Only the rows' lengths come home; the pattern tables are
+ * built out of the query corpus' payload on the device, no comparator exists and no query byte crosses PCIe.  Rows are sorted by length, cut
+ * into batches (RF_JOIN_BATCH) and evaluated 4 at a time by kernels that walk a work list in device memory: per batch one table build and
+ * one scan per query class that occurs (<= 32 / 33..64 symbols), however many groups of four the batch holds.  PER QUERY: every other row
+ * (longer rows, osa, damerau_levenshtein, hamming / prefix / postfix, general weight tables, a loose cutoff, a `char` corpus on either side)
+ * goes through rf_corpus_take, rf_comparator_new and rf_filter_u32, one row at a time -- slow by design, but no shape becomes an empty
+ * answer.  RF_TRACE_PLAN prints "[rf plan] join: m=.. batches=.. groups=.. per_query=.."; RF_JOIN=0 sends every row per query.
+ * Errors: a null queries / corpus / args / out_count, a null array with capacity != 0, an unknown order, op or flag bit, an f64-valued or
+ * unknown metric, args without a cutoff: RF_ERR_INVALID_ARG, decided before either corpus is looked at or a device is touched.  m == 0 is
+ * RF_OK and writes NOTHING, *out_count included, and this rule comes first: an empty `queries` with query_indices == NULL has m == 0.  Then: an index >= rf_corpus_count(queries), m != count with query_indices == NULL, m beyond 2^32 - 2, or
+ * corpora on different devices: RF_ERR_INVALID_ARG, nothing written.  Either corpus empty (and m != 0): RF_OK with *out_count = 0.
+ * Out of scope: f64 scores (normalized ops, fuzz ratio: the fused f64 kernels' keep rule is the obvious follow-up), device-resident output,
+ * a multi-GPU form (shards are separate calls with their bases; their triples concatenate), and a fused road for `char` corpora. */
+typedef enum rf_join_order { RF_JOIN_BY_QUERY = 0, RF_JOIN_ANY = 1 } rf_join_order;
+#define RF_JOIN_UPPER 1u
+rf_status rf_join_u32(rf_metric metric, const rf_corpus *queries, const uint64_t *query_indices, uint64_t m,
+                      const rf_corpus *corpus, rf_op op, const rf_args *args, uint32_t flags,
+                      uint64_t query_base, uint64_t index_base, uint64_t capacity,
+                      uint64_t *out_query, uint64_t *out_index, uint32_t *out_score, uint64_t *out_count,
+                      rf_join_order order, void *stream);
 
 /* ---- top-k ------------------------------------------------------------------------------------
  * The reference has no extract/top-k API; this is the engine's own reduction over the scores above,

@@ -276,6 +276,49 @@ class BatchComparator:
                 return [(idx[j, : min(int(cnt[j]), cap)].copy(), sc[j, : min(int(cnt[j]), cap)].copy()) for j in range(q)]
             cap = int(cnt.max())
 
+    @classmethod
+    def join(cls, queries: Corpus, corpus: Corpus, op: int, args: Optional[Args] = None, *, score_cutoff=None, query_indices=None, upper: bool = False,
+             order: int = N.JOIN_BY_QUERY, query_base: int = 0, index_base: int = 0, capacity: Optional[int] = None, weights=None, stream=None):
+        """Every pair (row of `queries`, candidate of `corpus`) within the cutoff (rf_join_u32): `(query_idx uint64[p], cand_idx uint64[p], scores uint32[p])`,
+        triple t being what `cls(row query_idx[t]).filter_many(op, corpus, ...)` reports for candidate cand_idx[t].  `queries` and `corpus` are packed corpora
+        and may be the same object (a self-join; `upper=True` then keeps each unordered pair once and no (i, i)).  `query_indices`: the rows to join, any
+        order, repeats allowed; None = every row.  A cutoff is required.  `capacity=None` counts first, then fetches everything; with a capacity the
+        arrays hold at most that many triples.  `last_join_count` (on the class the call was made through) holds the true number of pairs."""
+        if cls.FLOAT or op >= N.OP_NORMALIZED_DISTANCE:
+            raise ValueError("join: distance or similarity of the usize metrics only")
+        a = _mk_args(args, score_cutoff, None, weights, None)
+        ca = a.to_c(False)
+        if query_indices is None:
+            qi, m = None, len(queries)
+        else:
+            qi = np.ascontiguousarray(query_indices, dtype=np.uint64)
+            m = int(qi.size)
+        flags = N.JOIN_UPPER if upper else 0
+        cnt = C.c_uint64(0)
+
+        def call(cap, oq, oi, sc):
+            N.check(N.lib().rf_join_u32(cls.METRIC, queries._h, qi.ctypes.data if qi is not None and m else None, m, corpus._h, op, C.byref(ca), flags, query_base,
+                                        index_base, cap, oq.ctypes.data if cap else None, oi.ctypes.data if cap else None, sc.ctypes.data if cap else None,
+                                        C.byref(cnt), order, stream))
+
+        empty = (np.empty(0, dtype=np.uint64), np.empty(0, dtype=np.uint64), np.empty(0, dtype=np.uint32))
+        if capacity is None:
+            call(0, None, None, None)
+            cap = int(cnt.value)
+        else:
+            cap = int(capacity)
+        if cap == 0:
+            if capacity is not None:
+                call(0, None, None, None)
+            cls.last_join_count = int(cnt.value)
+            return empty
+        oq, oi, sc = np.empty(cap, dtype=np.uint64), np.empty(cap, dtype=np.uint64), np.empty(cap, dtype=np.uint32)
+        cnt.value = 0
+        call(cap, oq, oi, sc)
+        have = min(int(cnt.value), cap)
+        cls.last_join_count = int(cnt.value)
+        return oq[:have], oi[:have], sc[:have]
+
     def distance_many(self, corpus, args=None, **kw):
         return self.many(N.OP_DISTANCE, corpus, args, **kw)
 

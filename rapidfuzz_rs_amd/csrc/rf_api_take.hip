@@ -43,7 +43,7 @@ int rf_corpus_is_wide(const rf_corpus* c) { return c && c->wide ? 1 : 0; }
 
 // candidate -> slot of a length-bucketed corpus, built on first use under rf_corpus::Accel's rule (local owner, synchronize, then move under scratch_mu); the
 // gather path's copy serves when it is there.  The address never changes once handed out: the buffer only ever moves between the two owners.
-static rf_status corpus_take_slot_of(const rf_corpus* c, hipStream_t st, const uint32_t** out)
+rf_status corpus_take_slot_of(const rf_corpus* c, hipStream_t st, const uint32_t** out)
 {
     std::lock_guard<std::mutex> lock(c->scratch_mu);
     rf_corpus::Accel& a = c->accel;

@@ -512,6 +512,7 @@ RF_LOCAL std::vector<TileDesc> tiles_by_origin(const std::vector<TileDesc>& tile
 RF_LOCAL rf_status plan(const rf_comparator* c, const rf_corpus* corpus, rf_op op, const rf_args* args, bool f64_out, ScanParams* p, RawKind* raw);  // rf_api_scan.hip
 RF_LOCAL rf_status plan_multi(const MultiAsk& ask, const rf_comparator* const* cs, uint32_t q, const rf_corpus* corpus, rf_op op, const rf_args* args, MultiPlan* out);  // rf_api_topk_multi.hip
 RF_LOCAL rf_status check_multi_members(const char* fn, bool f64, const char* usize_only, const rf_comparator* const* cs, uint32_t q, rf_op op);  // rf_api_topk_multi.hip
+RF_LOCAL rf_status corpus_take_slot_of(const rf_corpus* c, hipStream_t st, const uint32_t** out);                        // rf_api_take.hip (length-bucketed corpora: candidate -> slot)
 RF_LOCAL const uint32_t* corpus_head6_plane(const rf_corpus* corpus, hipStream_t st);                                  // rf_api_scan.hip
 RF_LOCAL const uint32_t* corpus_data6(const rf_corpus* corpus, hipStream_t st);                                        // rf_api_scan.hip
 RF_LOCAL const uint8_t* corpus_head8_plane(const rf_corpus* corpus, const ScanParams& p, RawKind raw, hipStream_t st);    // rf_api_scan.hip

@@ -242,6 +242,36 @@ hipError_t launch_take_rows_len(const TakeParams& p, hipStream_t stream);  // id
 hipError_t launch_take_rows(const TakeParams& p, hipStream_t stream);      // row_slot, row_len, offsets -> out
 hipError_t launch_take_all(const TakeParams& p, hipStream_t stream);       // every candidate, walking tiles: offsets -> out
 
+// rf_join.hip: all pairs of two packed corpora within a tight cutoff (rf_join_u32).  The work list -- items, units, prefix table -- is rf_join_plan.hpp's.
+struct JoinItem;
+struct JoinPmParams {
+    ScanParams s;              // the QUERY corpus as load_tile reads it: data, tiles, uniform_len, uniform_tile_bytes
+    uint32_t n_slots;          // its slots: 64 per tile
+    const uint32_t* row_slot;  // [m] slot of every row of Q (take_rows_len_kernel leaves it)
+    const uint32_t* row_len;   // [m] ... and its length
+    const uint32_t* rows;      // [batch] table b is built for row rows[b] of Q
+    uint32_t batch;
+    const uint8_t* inv_sigma;  // 256 bytes: the query corpus' stored symbol -> the original byte
+    const uint8_t* sigma;      // 256 bytes: original byte -> the symbol the SCANNED corpus stores
+    uint64_t* tables;          // [batch][256]: bit i of row sigma[c] <=> symbol i of the query is c -- the rows the scan's LDS tables have
+};
+struct JoinParams {
+    ScanParams s;              // the scanned corpus, the finishing coefficients and the cutoff (plan()); len1 / tile_begin / tile_end are the items'
+    const JoinItem* items;     // device copies of a JoinList (rf_join_plan.hpp)
+    const uint32_t* prefix;
+    uint32_t n_items, n_units, span;
+    uint32_t batch;            // tables of the batch
+    const uint64_t* tables;
+    unsigned long long* count; // the call's counter: every pair, also beyond `cap`
+    uint64_t* pairs;           // [cap] position in Q << 32 | local candidate index ...
+    uint32_t* scores;          // [cap] ... and the score, for the first `cap` pairs to arrive
+    uint64_t cap;
+    uint32_t upper;            // RF_JOIN_UPPER: keep a pair only if candidate index > the query's row index
+};
+hipError_t launch_join_pm(const JoinPmParams& p, hipStream_t stream);
+// h_items / h_prefix: the host's copies of what jp.items / jp.prefix hold, checked (join_valid) before anything is launched
+hipError_t launch_join(RawKind raw, bool narrow, const JoinParams& jp, const JoinItem* h_items, const uint32_t* h_prefix, hipStream_t stream);
+
 // kernel launchers (rf_scan.hip, rf_long.hip, rf_damerau.hip, rf_compare.hip, rf_jaro.hip, rf_pack.hip)
 hipError_t launch_scan(RawKind raw, const ScanParams& p, hipStream_t stream, int* grid_used);
 hipError_t launch_osa1_asm(const ScanParams& p, hipStream_t stream, int grid);   // the same around the OSA column (OsaState<1>)

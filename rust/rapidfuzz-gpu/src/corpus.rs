@@ -99,6 +99,33 @@ impl Corpus {
         }
         Ok((0..m).map(|j| data[offsets[j] as usize..offsets[j + 1] as usize].to_vec()).collect())
     }
+    /// All pairs (row of `queries`, candidate of `self`) within the cutoff `args` carries (rf_join_u32): triples (query_base + row, index_base + candidate,
+    /// score), ascending by (position in `query_indices`, candidate).  `metric`: `RF_LEVENSHTEIN`, `RF_INDEL`, ... ; `op`: `RF_OP_DISTANCE` or
+    /// `RF_OP_SIMILARITY`; `query_indices`: the rows to join (any order, repeats allowed), `None` = every row; `upper`: keep a pair only if candidate >
+    /// row -- a self-join (`queries` is `self`) then reports each unordered pair once.  A pure count first, then one call with room for everything.
+    #[allow(clippy::too_many_arguments)]
+    pub fn join(&self, queries: &Corpus, metric: std::os::raw::c_int, op: std::os::raw::c_int, args: &RfArgs, query_indices: Option<&[u64]>, upper: bool, query_base: u64,
+                index_base: u64) -> Result<Vec<(u64, u64, usize)>, Error> {
+        let (qi, m) = match query_indices {
+            Some(v) if v.is_empty() => return Ok(Vec::new()),
+            Some(v) => (v.as_ptr(), v.len() as u64),
+            None => (std::ptr::null(), queries.len() as u64),
+        };
+        let flags = if upper { RF_JOIN_UPPER } else { 0 };
+        let null = std::ptr::null_mut();
+        let mut n = 0u64;
+        check(unsafe { rf_join_u32(metric, queries.0, qi, m, self.0, op, args, flags, query_base, index_base, 0, null, null, std::ptr::null_mut(), &mut n, RF_JOIN_BY_QUERY, std::ptr::null_mut()) })?;
+        let cap = n as usize;
+        if cap == 0 {
+            return Ok(Vec::new());
+        }
+        let (mut q, mut idx, mut val) = (vec![0u64; cap], vec![0u64; cap], vec![0u32; cap]);
+        check(unsafe {
+            rf_join_u32(metric, queries.0, qi, m, self.0, op, args, flags, query_base, index_base, n, q.as_mut_ptr(), idx.as_mut_ptr(), val.as_mut_ptr(), &mut n, RF_JOIN_BY_QUERY, std::ptr::null_mut())
+        })?;
+        let have = (n as usize).min(cap);
+        Ok((0..have).map(|t| (q[t], idx[t], val[t] as usize)).collect())
+    }
     /// The same as `String`s, for a corpus of `char`s (a byte corpus reads as Latin-1: its bytes are the code points 0..255).
     pub fn take_chars(&self, indices: &[u64], index_base: u64) -> Result<Vec<String>, Error> {
         if indices.is_empty() {
