@@ -169,10 +169,17 @@ struct Args {
     }
 };
 
+/// a triple of the joins by f64 score (rf_join_f64): `score` is the double normalized_*_filter_many (or the f64 metric's filter) reports for the pair
+struct JoinTripleF64 {
+    uint64_t query, candidate;
+    double score;
+};
+
 template <rf_metric M, bool FloatMetric>
 class BatchComparator {
 public:
     using usize_result = std::conditional_t<FloatMetric, double, size_t>;
+    using JoinTripleF64 = detail::JoinTripleF64;
     explicit BatchComparator(std::string_view s1)  // BatchComparator::new
     {
         check(rf_comparator_new(M, reinterpret_cast<const uint8_t*>(s1.data()), s1.size(), &h_));
@@ -306,20 +313,32 @@ public:
     // ---- all pairs of two packed corpora within the cutoff, one call (rf_join_u32): the triples (query row, candidate, score) -- what distance_filter_many of
     // a comparator over row `query` of `queries` reports for `candidate` -- ascending by (position in query_indices, candidate) or, RF_JOIN_ANY, as they arrived.
     // `queries` and `c` may be the same corpus (a self-join; `upper` then keeps each unordered pair once and no (i, i)).  query_indices: the rows to join, nullptr = every row (an empty list: no pair).  The
-    // cutoff is required.  usize metrics only.
+    // cutoff is required.  The usize metrics' triples carry a size_t (rf_join_u32); jaro / jaro_winkler's, and every normalized_*_join's, a double (rf_join_f64).
     struct JoinTriple {
         uint64_t query, candidate;
         size_t score;
     };
-    static std::vector<JoinTriple> distance_join(const Corpus& queries, const Corpus& c, const Args<usize_result>& a, bool upper = false, rf_join_order order = RF_JOIN_BY_QUERY,
+    using join_result = std::conditional_t<FloatMetric, JoinTripleF64, JoinTriple>;
+    static std::vector<join_result> distance_join(const Corpus& queries, const Corpus& c, const Args<usize_result>& a, bool upper = false, rf_join_order order = RF_JOIN_BY_QUERY,
                                                  const std::vector<uint64_t>* query_indices = nullptr, uint64_t query_base = 0, uint64_t index_base = 0)
     {
-        return join(queries, c, RF_OP_DISTANCE, a.to_c(), upper, order, query_indices, query_base, index_base);
+        return join<join_result>(queries, c, RF_OP_DISTANCE, a.to_c(), upper, order, query_indices, query_base, index_base);
     }
-    static std::vector<JoinTriple> similarity_join(const Corpus& queries, const Corpus& c, const Args<usize_result>& a, bool upper = false, rf_join_order order = RF_JOIN_BY_QUERY,
+    static std::vector<join_result> similarity_join(const Corpus& queries, const Corpus& c, const Args<usize_result>& a, bool upper = false, rf_join_order order = RF_JOIN_BY_QUERY,
                                                    const std::vector<uint64_t>* query_indices = nullptr, uint64_t query_base = 0, uint64_t index_base = 0)
     {
-        return join(queries, c, RF_OP_SIMILARITY, a.to_c(), upper, order, query_indices, query_base, index_base);
+        return join<join_result>(queries, c, RF_OP_SIMILARITY, a.to_c(), upper, order, query_indices, query_base, index_base);
+    }
+    // ---- the same by normalized score (rf_join_f64): "every pair with normalized_similarity >= 0.9" -- bit for bit the doubles normalized_*_filter_many reports
+    static std::vector<JoinTripleF64> normalized_distance_join(const Corpus& queries, const Corpus& c, const Args<double>& a, bool upper = false, rf_join_order order = RF_JOIN_BY_QUERY,
+                                                               const std::vector<uint64_t>* query_indices = nullptr, uint64_t query_base = 0, uint64_t index_base = 0)
+    {
+        return join<JoinTripleF64>(queries, c, RF_OP_NORMALIZED_DISTANCE, a.to_c(), upper, order, query_indices, query_base, index_base);
+    }
+    static std::vector<JoinTripleF64> normalized_similarity_join(const Corpus& queries, const Corpus& c, const Args<double>& a, bool upper = false, rf_join_order order = RF_JOIN_BY_QUERY,
+                                                                 const std::vector<uint64_t>* query_indices = nullptr, uint64_t query_base = 0, uint64_t index_base = 0)
+    {
+        return join<JoinTripleF64>(queries, c, RF_OP_NORMALIZED_SIMILARITY, a.to_c(), upper, order, query_indices, query_base, index_base);
     }
 
     // ---- the reference's per-candidate methods (a one-candidate corpus through the same kernels)
@@ -426,24 +445,34 @@ private:
             return res;
         }
     }
-    static std::vector<JoinTriple> join(const Corpus& queries, const Corpus& c, rf_op op, const rf_args& a, bool upper, rf_join_order order,
-                                        const std::vector<uint64_t>* query_indices, uint64_t query_base, uint64_t index_base)
+    // (every *_join: Triple picks the call -- JoinTriple rf_join_u32, JoinTripleF64 rf_join_f64)
+    template <class Triple>
+    static std::vector<Triple> join(const Corpus& queries, const Corpus& c, rf_op op, const rf_args& a, bool upper, rf_join_order order,
+                                    const std::vector<uint64_t>* query_indices, uint64_t query_base, uint64_t index_base)
     {
-        static_assert(!FloatMetric, "rf_join_u32 serves the usize-valued metrics");
+        constexpr bool f64 = std::is_same_v<Triple, JoinTripleF64>;
+        static_assert(f64 || !FloatMetric, "rf_join_u32 serves the usize-valued metrics");
+        using Score = std::conditional_t<f64, double, uint32_t>;
         if (query_indices && query_indices->empty()) return {};  // (an empty selection is no pair; only a null pointer asks for every row)
         const uint64_t* qi = query_indices ? query_indices->data() : nullptr;
         const uint64_t m = query_indices ? query_indices->size() : queries.size();
         const uint32_t flags = upper ? RF_JOIN_UPPER : 0u;
-        uint64_t count = 0;  // (a pure count first: the call reports the true number of pairs)
-        check(rf_join_u32(M, queries.handle(), qi, m, c.handle(), op, &a, flags, query_base, index_base, 0, nullptr, nullptr, nullptr, &count, order, nullptr));
-        std::vector<JoinTriple> res;
+        uint64_t count = 0;
+        auto call = [&](uint64_t cap, uint64_t* query, uint64_t* index, Score* score) {
+            if constexpr (f64)
+                check(rf_join_f64(M, queries.handle(), qi, m, c.handle(), op, &a, flags, query_base, index_base, cap, query, index, score, &count, order, nullptr));
+            else
+                check(rf_join_u32(M, queries.handle(), qi, m, c.handle(), op, &a, flags, query_base, index_base, cap, query, index, score, &count, order, nullptr));
+        };
+        call(0, nullptr, nullptr, nullptr);  // (a pure count first: the call reports the true number of pairs)
+        std::vector<Triple> res;
         if (count == 0) return res;
         std::vector<uint64_t> query(count), index(count);
-        std::vector<uint32_t> score(count);
+        std::vector<Score> score(count);
         const uint64_t cap = count;
-        check(rf_join_u32(M, queries.handle(), qi, m, c.handle(), op, &a, flags, query_base, index_base, cap, query.data(), index.data(), score.data(), &count, order, nullptr));
+        call(cap, query.data(), index.data(), score.data());
         res.reserve(std::min(cap, count));
-        for (uint64_t t = 0; t < std::min(cap, count); ++t) res.push_back(JoinTriple{query[t], index[t], (size_t)score[t]});
+        for (uint64_t t = 0; t < std::min(cap, count); ++t) res.push_back(Triple{query[t], index[t], (decltype(Triple::score))score[t]});
         return res;
     }
     static std::vector<std::vector<std::pair<uint64_t, double>>> filter_multi_f64(const std::vector<const BatchComparator*>& scorers, const Corpus& c, rf_op op,
@@ -556,6 +585,19 @@ public:
         std::vector<const detail::BatchComparator<RF_FUZZ_RATIO, true>*> inner;
         for (const RatioBatchComparator* s : scorers) inner.push_back(&s->c_);
         return detail::BatchComparator<RF_FUZZ_RATIO, true>::normalized_similarity_filter_multi(inner, c, a, order, index_base);
+    }
+    /// every pair (row of `queries`, candidate of `c`) whose ratio reaches the cutoff, one call (rf_join_f64); see BatchComparator::distance_join
+    using JoinTripleF64 = detail::JoinTripleF64;
+    static std::vector<JoinTripleF64> similarity_join(const Corpus& queries, const Corpus& c, const detail::Args<double>& a, bool upper = false, rf_join_order order = RF_JOIN_BY_QUERY,
+                                                      const std::vector<uint64_t>* query_indices = nullptr, uint64_t query_base = 0, uint64_t index_base = 0)
+    {
+        return detail::BatchComparator<RF_FUZZ_RATIO, true>::similarity_join(queries, c, a, upper, order, query_indices, query_base, index_base);
+    }
+    static std::vector<JoinTripleF64> normalized_similarity_join(const Corpus& queries, const Corpus& c, const detail::Args<double>& a, bool upper = false,
+                                                                 rf_join_order order = RF_JOIN_BY_QUERY, const std::vector<uint64_t>* query_indices = nullptr,
+                                                                 uint64_t query_base = 0, uint64_t index_base = 0)
+    {
+        return detail::BatchComparator<RF_FUZZ_RATIO, true>::normalized_similarity_join(queries, c, a, upper, order, query_indices, query_base, index_base);
     }
 
 private:

@@ -73,8 +73,8 @@
  *   RF_TOPK_MULTI                 1         0: rf_topk_multi_u32 / _f64 send every query through rf_topk_u32 / _f64 instead of fusing 4 (or 2) to a pass over the corpus
  *   RF_FILTER_MULTI               1         0: rf_filter_multi_u32 / _f64 send every query through rf_filter_u32 / _f64 instead of fusing tight-cutoff queries 4 (or 2) to a pass over the corpus
  *   RF_FILTER_MULTI_F64_ROUTE     1         0: rf_filter_multi_f64 fuses every fusable query, also the shapes its measured routing rules send through rf_filter_f64 (A/B measurements)
- *   RF_JOIN                       1         0: rf_join_u32 sends every row of Q through rf_corpus_take + rf_filter_u32 instead of the device road (identical results)
- *   RF_JOIN_BATCH                 16384     most rows of Q per device batch of rf_join_u32 (2 KiB of table scratch per row; 1 .. 1048576)
+ *   RF_JOIN                       1         0: rf_join_u32 / rf_join_f64 send every row of Q through rf_corpus_take + rf_filter_u32 / rf_filter_f64 instead of the device road (identical results; both calls read it)
+ *   RF_JOIN_BATCH                 16384     most rows of Q per device batch of rf_join_u32 / rf_join_f64 (2 KiB of table scratch per row; 1 .. 1048576; both calls read it)
  *   RF_JARO_PRIV                  0         1: Jaro asm kernel gathers from a conflict-free copy of the pattern table (corpora of <= 64 symbols; measured: no gain)
  *   RF_WF_REG                     1         0: LDS rows instead of register rows for generalized weights, queries <= 64
  *   RF_TRANSLATE_DIRECT           1         0: staged translation of u32 overflow symbols
@@ -606,7 +606,7 @@ rf_status rf_filter_multi_f64(const rf_comparator *const *cs, uint32_t q, const 
  * unknown metric, args without a cutoff: RF_ERR_INVALID_ARG, decided before either corpus is looked at or a device is touched.  m == 0 is
  * RF_OK and writes NOTHING, *out_count included, and this rule comes first: an empty `queries` with query_indices == NULL has m == 0.  Then: an index >= rf_corpus_count(queries), m != count with query_indices == NULL, m beyond 2^32 - 2, or
  * corpora on different devices: RF_ERR_INVALID_ARG, nothing written.  Either corpus empty (and m != 0): RF_OK with *out_count = 0.
- * Out of scope: f64 scores (normalized ops, fuzz ratio: the fused f64 kernels' keep rule is the obvious follow-up), device-resident output,
+ * Out of scope: f64 scores (normalized ops, fuzz ratio, jaro / jaro_winkler: rf_join_f64 below), device-resident output,
  * a multi-GPU form (shards are separate calls with their bases; their triples concatenate), and a fused road for `char` corpora. */
 typedef enum rf_join_order { RF_JOIN_BY_QUERY = 0, RF_JOIN_ANY = 1 } rf_join_order;
 #define RF_JOIN_UPPER 1u
@@ -614,6 +614,38 @@ rf_status rf_join_u32(rf_metric metric, const rf_corpus *queries, const uint64_t
                       const rf_corpus *corpus, rf_op op, const rf_args *args, uint32_t flags,
                       uint64_t query_base, uint64_t index_base, uint64_t capacity,
                       uint64_t *out_query, uint64_t *out_index, uint32_t *out_score, uint64_t *out_count,
+                      rf_join_order order, void *stream);
+
+/* ---- join by f64 score: all pairs of two packed corpora within a normalized cutoff ---------------------
+ * "Every pair with normalized_similarity >= 0.9", "every pair with fuzz::ratio >= 0.9": rf_join_u32's contract, word for word, wherever it
+ * does not concern the score type.  Q and query_indices (any order, repeats, NULL = every row), the same handle on both sides,
+ * RF_JOIN_UPPER on the local indices, the bases, *out_count ALWAYS the true count, capacity == 0 a pure count, the two orders, m == 0 first
+ * and writing nothing, a call that does not return RF_OK writing nothing: all as above.  The triple (query_base + qi, index_base + j, v)
+ * holds exactly the double rf_filter_f64(rf_comparator_new(metric, the bytes of row qi), corpus, op, args, ...) returns for candidate j,
+ * bit for bit, with the same None rule under args->cutoff_f64.  Accepted (metric, op) pairs are rf_filter_multi_f64's:
+ * RF_OP_NORMALIZED_DISTANCE / RF_OP_NORMALIZED_SIMILARITY of the usize metrics, RF_FUZZ_RATIO with its two similarity ops (with and without
+ * RF_FLAG_RATIO_INDEL_NORMALIZATION), every op of RF_JARO / RF_JARO_WINKLER.  args->cutoff_f64 must not be NaN: without a cutoff the answer
+ * is all m x n pairs.
+ * `capacity` is ALLOCATED as given -- 16 bytes per entry on the device here (the 8-byte pair and the double itself; at most m x n entries)
+ * and 32 per entry on the host beside the caller's arrays while the call runs -- so count first (capacity 0) when the answer cannot be bounded.
+ * Two roads, the u32 call's.  On the DEVICE: both corpora hold bytes, levenshtein (uniform or Indel-like weights) / indel / lcs_seq / fuzz
+ * ratio, rows of <= 64 symbols whose f64 cutoff is TIGHT (the planner's early-out rule: an allowed normalized distance below 0.7 for
+ * levenshtein, below 0.4 for the LCS family).  The same batches, work list and kernels with the f64 keep rule of the single-query call at
+ * a tile's end; the kernel stores the double itself, so -- unlike rf_filter_multi_f64 / rf_topk_multi_f64, which order 32-bit keys -- no
+ * maximum is too large: the corpus may hold candidates of any length.  PER QUERY: every other row (jaro, jaro_winkler, osa,
+ * damerau_levenshtein, hamming / prefix / postfix, general weight tables, longer rows, a loose cutoff, a `char` corpus on either side)
+ * goes through rf_corpus_take, rf_comparator_new and rf_filter_f64, one row at a time.  RF_TRACE_PLAN prints
+ * "[rf plan] join_f64: m=.. batches=.. groups=.. per_query=.."; RF_JOIN=0 and RF_JOIN_BATCH act as above.
+ * Errors: rf_join_u32's null pointers, an unknown order, op, flag bit or metric, RF_OP_DISTANCE / RF_OP_SIMILARITY of a usize metric
+ * (u32-valued: rf_join_u32), a distance op of fuzz ratio, a NaN cutoff: RF_ERR_INVALID_ARG, decided before either corpus is looked at or a
+ * device is touched, nothing written.  Then, as above: an index out of range, m != count with query_indices == NULL, m beyond 2^32 - 2,
+ * corpora on different devices: RF_ERR_INVALID_ARG; either corpus empty (and m != 0): RF_OK with *out_count = 0.
+ * Out of scope: a host-built integer limit per (query length, tile length) in place of the f64 division of every look, device-resident
+ * output, a multi-GPU form, and a fused road for `char` corpora. */
+rf_status rf_join_f64(rf_metric metric, const rf_corpus *queries, const uint64_t *query_indices, uint64_t m,
+                      const rf_corpus *corpus, rf_op op, const rf_args *args, uint32_t flags,
+                      uint64_t query_base, uint64_t index_base, uint64_t capacity,
+                      uint64_t *out_query, uint64_t *out_index, double *out_score, uint64_t *out_count,
                       rf_join_order order, void *stream);
 
 /* ---- top-k ------------------------------------------------------------------------------------

@@ -285,9 +285,26 @@ class BatchComparator:
         order, repeats allowed; None = every row.  A cutoff is required.  `capacity=None` counts first, then fetches everything; with a capacity the
         arrays hold at most that many triples.  `last_join_count` (on the class the call was made through) holds the true number of pairs."""
         if cls.FLOAT or op >= N.OP_NORMALIZED_DISTANCE:
-            raise ValueError("join: distance or similarity of the usize metrics only")
-        a = _mk_args(args, score_cutoff, None, weights, None)
-        ca = a.to_c(False)
+            raise ValueError("join: distance or similarity of the usize metrics only (normalized_*, jaro, jaro_winkler, ratio: join_f64)")
+        return cls._join(False, queries, corpus, op, _mk_args(args, score_cutoff, None, weights, None), query_indices, upper, order, query_base, index_base, capacity, stream)
+
+    @classmethod
+    def join_f64(cls, queries: Corpus, corpus: Corpus, op: int, args: Optional[Args] = None, *, score_cutoff=None, query_indices=None, upper: bool = False,
+                 order: int = N.JOIN_BY_QUERY, query_base: int = 0, index_base: int = 0, capacity: Optional[int] = None, weights=None, stream=None):
+        """`join` by f64 score (rf_join_f64): `(query_idx uint64[p], cand_idx uint64[p], scores float64[p])`, triple t holding exactly the double
+        `cls(row query_idx[t]).filter_many(op, corpus, ...)` reports for candidate cand_idx[t].  op: normalized_distance / normalized_similarity of the usize
+        metrics, similarity / normalized_similarity of `fuzz.RatioBatchComparator`, any op of jaro / jaro_winkler.  Every other argument, the count-then-fetch
+        protocol and `last_join_count` are `join`'s."""
+        if not cls.FLOAT and op < N.OP_NORMALIZED_DISTANCE:
+            raise ValueError("join_f64: distance and similarity of the usize metrics are uint32-valued (join)")
+        return cls._join(True, queries, corpus, op, _mk_args(args, score_cutoff, None, weights, None), query_indices, upper, order, query_base, index_base, capacity, stream)
+
+    @classmethod
+    def _join(cls, is_f: bool, queries: Corpus, corpus: Corpus, op: int, a: Args, query_indices, upper, order, query_base, index_base, capacity, stream):
+        """what `join` and `join_f64` share: count first, then fetch"""
+        ca = a.to_c(is_f)
+        fn = N.lib().rf_join_f64 if is_f else N.lib().rf_join_u32
+        score_t = np.float64 if is_f else np.uint32
         if query_indices is None:
             qi, m = None, len(queries)
         else:
@@ -297,11 +314,11 @@ class BatchComparator:
         cnt = C.c_uint64(0)
 
         def call(cap, oq, oi, sc):
-            N.check(N.lib().rf_join_u32(cls.METRIC, queries._h, qi.ctypes.data if qi is not None and m else None, m, corpus._h, op, C.byref(ca), flags, query_base,
-                                        index_base, cap, oq.ctypes.data if cap else None, oi.ctypes.data if cap else None, sc.ctypes.data if cap else None,
-                                        C.byref(cnt), order, stream))
+            N.check(fn(cls.METRIC, queries._h, qi.ctypes.data if qi is not None and m else None, m, corpus._h, op, C.byref(ca), flags, query_base,
+                       index_base, cap, oq.ctypes.data if cap else None, oi.ctypes.data if cap else None, sc.ctypes.data if cap else None,
+                       C.byref(cnt), order, stream))
 
-        empty = (np.empty(0, dtype=np.uint64), np.empty(0, dtype=np.uint64), np.empty(0, dtype=np.uint32))
+        empty = (np.empty(0, dtype=np.uint64), np.empty(0, dtype=np.uint64), np.empty(0, dtype=score_t))
         if capacity is None:
             call(0, None, None, None)
             cap = int(cnt.value)
@@ -312,7 +329,7 @@ class BatchComparator:
                 call(0, None, None, None)
             cls.last_join_count = int(cnt.value)
             return empty
-        oq, oi, sc = np.empty(cap, dtype=np.uint64), np.empty(cap, dtype=np.uint64), np.empty(cap, dtype=np.uint32)
+        oq, oi, sc = np.empty(cap, dtype=np.uint64), np.empty(cap, dtype=np.uint64), np.empty(cap, dtype=score_t)
         cnt.value = 0
         call(cap, oq, oi, sc)
         have = min(int(cnt.value), cap)

@@ -242,7 +242,7 @@ hipError_t launch_take_rows_len(const TakeParams& p, hipStream_t stream);  // id
 hipError_t launch_take_rows(const TakeParams& p, hipStream_t stream);      // row_slot, row_len, offsets -> out
 hipError_t launch_take_all(const TakeParams& p, hipStream_t stream);       // every candidate, walking tiles: offsets -> out
 
-// rf_join.hip: all pairs of two packed corpora within a tight cutoff (rf_join_u32).  The work list -- items, units, prefix table -- is rf_join_plan.hpp's.
+// rf_join.hip: all pairs of two packed corpora within a tight cutoff (rf_join_u32 / rf_join_f64).  The work list -- items, units, prefix table -- is rf_join_plan.hpp's.
 struct JoinItem;
 struct JoinPmParams {
     ScanParams s;              // the QUERY corpus as load_tile reads it: data, tiles, uniform_len, uniform_tile_bytes
@@ -267,6 +267,9 @@ struct JoinParams {
     uint32_t* scores;          // [cap] ... and the score, for the first `cap` pairs to arrive
     uint64_t cap;
     uint32_t upper;            // RF_JOIN_UPPER: keep a pair only if candidate index > the query's row index
+    // (rf_join_f64's two come last: the u32 kernels read every field above at the offset it always had)
+    uint32_t norm;             // s is an f64 plan of a normalized op under a cutoff: keep by norm_dist / norm_keep, store into scores_f64
+    double* scores_f64;        // [cap] the double emit_fin would have written, in place of `scores`
 };
 hipError_t launch_join_pm(const JoinPmParams& p, hipStream_t stream);
 // h_items / h_prefix: the host's copies of what jp.items / jp.prefix hold, checked (join_valid) before anything is launched

@@ -1,4 +1,4 @@
-// rf_join.hip -- all pairs of two packed corpora within a tight cutoff (rf_join_u32; host side in rf_api_join.hip, the work list in rf_join_plan.hpp).
+// rf_join.hip -- all pairs of two packed corpora within a tight cutoff (rf_join_u32 / rf_join_f64; host side in rf_api_join.hip, the work list in rf_join_plan.hpp).
 //   join_pm_kernel   a batch of B queries straight out of the QUERY corpus' packed payload (rf_take_addr.hpp's addresses, un-renamed through that corpus'
 //                    inverse sigma as rf_take.hip does) into B single-word pattern tables of 256 x u64, written AT THE SCANNED CORPUS' SIGMA ROWS: row sigma[c]
 //                    of table b has bit i set when symbol i of query b is c.  That is the form the scans keep in LDS, so join_kernel stages a table with a
@@ -10,6 +10,9 @@
 //                    BARRIERS: the unit loop's trip count depends on blockIdx.x alone, nothing inside it returns or breaks out, and a wavefront without a tile
 //                    in a unit skips the walk and nothing else -- every wavefront of the workgroup reaches both barriers of every unit.
 //                    Emission: the counted append (append_passers' scheme) onto ONE 64-bit counter and one capacity-bounded triple buffer for the whole call.
+//                    kNorm (rf_join_f64): jp.s is an f64 plan, so the looks already run may_pass()'s f64 compare; at a tile's end a member is kept by
+//                    norm_dist / norm_keep (rf_device.hpp) and the double emit_fin would have written goes into the f64 score buffer -- no key, so no
+//                    limit on the maximum.
 // Plain vector stores only; no inline assembly.
 // Product code: never includes or links anything from oracle/.
 #include <algorithm>
@@ -60,8 +63,8 @@ hipError_t launch_join_pm(const JoinPmParams& p, hipStream_t stream)
 }
 
 // the counted append onto the call's buffers: one 64-bit atomic per wavefront that holds a passer
-template <class Pair>
-__device__ __forceinline__ void append_triples(const JoinParams& jp, bool pass, uint32_t lane, uint32_t score, Pair&& pair)
+template <class Score, class Pair>
+__device__ __forceinline__ void append_triples(const JoinParams& jp, Score* scores, bool pass, uint32_t lane, Score score, Pair&& pair)
 {
     const uint64_t m = __ballot(pass);
     if (!m) return;
@@ -71,11 +74,11 @@ __device__ __forceinline__ void append_triples(const JoinParams& jp, bool pass, 
     const unsigned long long at = base + (uint32_t)__popcll(m & ((1ull << lane) - 1));
     if (pass && at < jp.cap) {
         jp.pairs[at] = pair();
-        jp.scores[at] = score;
+        scores[at] = score;
     }
 }
 
-template <class State, bool kUniform>
+template <class State, bool kUniform, bool kNorm>
 __global__ __launch_bounds__(kWave* kWavesPerBlock) void join_kernel(const JoinParams jp)
 {
     static_assert(State::kWords == 1, "multi-query kernels are single-word");
@@ -163,10 +166,20 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void join_kernel(const JoinP
                 for (int q = 0; q < Q; ++q) {
                     if (!(live & (1u << q))) continue;
                     const uint32_t raw = st[q].result(len1[q], len2);
-                    bool keep;
-                    const uint32_t v = usize_value(p, fin[q], raw, &keep);
-                    const bool pass = valid && keep && (!jp.upper || idx > qidx[q]);
-                    append_triples(jp, pass, lane, v, [&] { return ((uint64_t)qpos[q] << 32) | idx; });
+                    if constexpr (!kNorm) {
+                        bool keep;
+                        const uint32_t v = usize_value(p, fin[q], raw, &keep);
+                        const bool pass = valid && keep && (!jp.upper || idx > qidx[q]);
+                        append_triples(jp, jp.scores, pass, lane, v, [&] { return ((uint64_t)qpos[q] << 32) | idx; });
+                    } else {
+                        // (has_cutoff: the launcher takes plans under a cutoff only.  What is stored is what emit_fin writes: nd, or 1.0 - nd for the similarity)
+                        TileFin f = fin[q];
+                        f.max = uniform(f.max);
+                        const double nd = norm_dist(p, f, raw).nd;
+                        const bool pass = valid && norm_keep(p, nd) && (!jp.upper || idx > qidx[q]);
+                        const double v = p.op == RF_OP_NORMALIZED_DISTANCE ? nd : 1.0 - nd;
+                        append_triples(jp, jp.scores_f64, pass, lane, v, [&] { return ((uint64_t)qpos[q] << 32) | idx; });
+                    }
                 }
 
                 if (!has_next) break;  // (leaves the tile walk, never the unit loop)
@@ -184,16 +197,25 @@ hipError_t launch_join(RawKind raw, bool narrow, const JoinParams& jp, const Joi
 {
     const ScanParams& p = jp.s;
     if (jp.n_items == 0 || jp.n_units == 0) return hipSuccess;
-    if (!h_items || !h_prefix || !jp.items || !jp.prefix || !jp.tables || !jp.count || (jp.cap && (!jp.pairs || !jp.scores)) || p.out_f64 || !p.has_cutoff) return hipErrorInvalidValue;
+    if (!h_items || !h_prefix || !jp.items || !jp.prefix || !jp.tables || !jp.count || !p.has_cutoff) return hipErrorInvalidValue;
+    if (jp.norm ? !(p.out_f64 && (p.op == RF_OP_NORMALIZED_DISTANCE || p.op == RF_OP_NORMALIZED_SIMILARITY)) : p.out_f64 != 0) return hipErrorInvalidValue;
+    if (jp.cap && (!jp.pairs || (jp.norm ? !jp.scores_f64 : !jp.scores))) return hipErrorInvalidValue;
     if (!p.data || (p.tiles && !p.orig)) return hipErrorInvalidValue;
     if (!join_valid(h_items, h_prefix, jp.n_items, jp.n_units, p.n_tiles, jp.batch, narrow, jp.span)) return hipErrorInvalidValue;
     const dim3 g(std::max(1u, std::min<uint32_t>(jp.n_units, (uint32_t)scan_max_grid()))), b(kWave * kWavesPerBlock);
     auto with_state = [&](auto state) {
         using State = typename decltype(state)::type;
-        if (p.tiles)
-            hipLaunchKernelGGL((join_kernel<State, false>), g, b, 0, stream, jp);
-        else
-            hipLaunchKernelGGL((join_kernel<State, true>), g, b, 0, stream, jp);
+        if (jp.norm) {
+            if (p.tiles)
+                hipLaunchKernelGGL((join_kernel<State, false, true>), g, b, 0, stream, jp);
+            else
+                hipLaunchKernelGGL((join_kernel<State, true, true>), g, b, 0, stream, jp);
+        } else {
+            if (p.tiles)
+                hipLaunchKernelGGL((join_kernel<State, false, false>), g, b, 0, stream, jp);
+            else
+                hipLaunchKernelGGL((join_kernel<State, true, false>), g, b, 0, stream, jp);
+        }
         return hipGetLastError();
     };
     if (raw == RAW_LEV) return narrow ? with_state(MultiStateTag<Lev32State>{}) : with_state(MultiStateTag<LevState<1>>{});

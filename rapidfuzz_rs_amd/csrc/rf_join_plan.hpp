@@ -1,4 +1,4 @@
-// rf_join_plan.hpp -- the work list of rf_join_u32 (rf_api_join.hip builds it, rf_join.hip join_kernel walks it): which queries of a batch share a work item,
+// rf_join_plan.hpp -- the work list of rf_join_u32 / rf_join_f64 (rf_api_join.hip builds it, rf_join.hip join_kernel walks it): which queries of a batch share a work item,
 // which tiles an item visits, and which workgroup unit walks which part of them.  Plain arithmetic, no HIP call: the host and the kernel compile the same
 // join_unit(), and a host-compiled test (tests/cpp/join_plan_check.cpp) checks all of it without a device.
 //

@@ -126,6 +126,32 @@ impl Corpus {
         let have = (n as usize).min(cap);
         Ok((0..have).map(|t| (q[t], idx[t], val[t] as usize)).collect())
     }
+    /// `join` by f64 score (rf_join_f64): `op` is `RF_OP_NORMALIZED_DISTANCE` / `RF_OP_NORMALIZED_SIMILARITY` of a usize metric, a similarity op of
+    /// `RF_FUZZ_RATIO`, or any op of `RF_JARO` / `RF_JARO_WINKLER`; `args.cutoff_f64` carries the cutoff.  The scores are the doubles the single-query
+    /// filter reports, bit for bit.
+    #[allow(clippy::too_many_arguments)]
+    pub fn join_f64(&self, queries: &Corpus, metric: std::os::raw::c_int, op: std::os::raw::c_int, args: &RfArgs, query_indices: Option<&[u64]>, upper: bool, query_base: u64,
+                    index_base: u64) -> Result<Vec<(u64, u64, f64)>, Error> {
+        let (qi, m) = match query_indices {
+            Some(v) if v.is_empty() => return Ok(Vec::new()),
+            Some(v) => (v.as_ptr(), v.len() as u64),
+            None => (std::ptr::null(), queries.len() as u64),
+        };
+        let flags = if upper { RF_JOIN_UPPER } else { 0 };
+        let null = std::ptr::null_mut();
+        let mut n = 0u64;
+        check(unsafe { rf_join_f64(metric, queries.0, qi, m, self.0, op, args, flags, query_base, index_base, 0, null, null, std::ptr::null_mut(), &mut n, RF_JOIN_BY_QUERY, std::ptr::null_mut()) })?;
+        let cap = n as usize;
+        if cap == 0 {
+            return Ok(Vec::new());
+        }
+        let (mut q, mut idx, mut val) = (vec![0u64; cap], vec![0u64; cap], vec![0f64; cap]);
+        check(unsafe {
+            rf_join_f64(metric, queries.0, qi, m, self.0, op, args, flags, query_base, index_base, n, q.as_mut_ptr(), idx.as_mut_ptr(), val.as_mut_ptr(), &mut n, RF_JOIN_BY_QUERY, std::ptr::null_mut())
+        })?;
+        let have = (n as usize).min(cap);
+        Ok((0..have).map(|t| (q[t], idx[t], val[t])).collect())
+    }
     /// The same as `String`s, for a corpus of `char`s (a byte corpus reads as Latin-1: its bytes are the code points 0..255).
     pub fn take_chars(&self, indices: &[u64], index_base: u64) -> Result<Vec<String>, Error> {
         if indices.is_empty() {
