@@ -341,6 +341,24 @@ public:
         return join<JoinTripleF64>(queries, c, RF_OP_NORMALIZED_SIMILARITY, a.to_c(), upper, order, query_indices, query_base, index_base);
     }
 
+    // ---- the k best candidates of `c` for every row of the packed corpus `queries`, one call (rf_join_topk_u32): res[j] = (index_base + index, score) pairs of row
+    // query_indices[j] (nullptr = every row; an empty list: no row) -- what distance_topk_multi of a comparator over that row returns, ordered by (score ascending,
+    // index ascending), at most k of them.  No cutoff is needed.  `queries` and `c` may be the same corpus; `no_self` then never offers a row its own candidate
+    // (compared by row index), so every record gets its k nearest OTHER records.  usize metrics only.
+    static std::vector<std::vector<std::pair<uint64_t, size_t>>> distance_join_topk(const Corpus& queries, const Corpus& c, uint32_t k, const Args<usize_result>& a = {},
+                                                                                     bool no_self = false, const std::vector<uint64_t>* query_indices = nullptr,
+                                                                                     uint64_t index_base = 0)
+    {
+        return join_topk(queries, c, k, RF_OP_DISTANCE, a.to_c(), no_self, query_indices, index_base);
+    }
+    /// the same by similarity: (score descending, index ascending)
+    static std::vector<std::vector<std::pair<uint64_t, size_t>>> similarity_join_topk(const Corpus& queries, const Corpus& c, uint32_t k, const Args<usize_result>& a = {},
+                                                                                       bool no_self = false, const std::vector<uint64_t>* query_indices = nullptr,
+                                                                                       uint64_t index_base = 0)
+    {
+        return join_topk(queries, c, k, RF_OP_SIMILARITY, a.to_c(), no_self, query_indices, index_base);
+    }
+
     // ---- the reference's per-candidate methods (a one-candidate corpus through the same kernels)
     std::optional<usize_result> distance_with_args(std::string_view s2, const Args<usize_result>& a) const
     {
@@ -444,6 +462,21 @@ private:
                 for (uint64_t m = 0; m < count[j]; ++m) res[j].emplace_back(index[j * cap + m], (size_t)score[j * cap + m]);
             return res;
         }
+    }
+    static std::vector<std::vector<std::pair<uint64_t, size_t>>> join_topk(const Corpus& queries, const Corpus& c, uint32_t k, rf_op op, const rf_args& a, bool no_self,
+                                                                           const std::vector<uint64_t>* query_indices, uint64_t index_base)
+    {
+        static_assert(!FloatMetric, "rf_join_topk_u32 serves the usize-valued metrics");
+        if (query_indices && query_indices->empty()) return {};  // (an empty selection is no row; only a null pointer asks for every row)
+        const uint64_t* qi = query_indices ? query_indices->data() : nullptr;
+        const uint64_t m = query_indices ? query_indices->size() : queries.size();
+        std::vector<uint32_t> score(m * k), count(m);
+        std::vector<uint64_t> index(m * k);
+        check(rf_join_topk_u32(M, queries.handle(), qi, m, c.handle(), op, &a, no_self ? RF_JOIN_NO_SELF : 0u, k, index_base, score.data(), index.data(), count.data(), nullptr));
+        std::vector<std::vector<std::pair<uint64_t, size_t>>> res(m);
+        for (size_t j = 0; j < m; ++j)
+            for (uint32_t t = 0; t < count[j]; ++t) res[j].emplace_back(index[j * k + t], (size_t)score[j * k + t]);
+        return res;
     }
     // (every *_join: Triple picks the call -- JoinTriple rf_join_u32, JoinTripleF64 rf_join_f64)
     template <class Triple>

@@ -74,7 +74,12 @@
  *   RF_FILTER_MULTI               1         0: rf_filter_multi_u32 / _f64 send every query through rf_filter_u32 / _f64 instead of fusing tight-cutoff queries 4 (or 2) to a pass over the corpus
  *   RF_FILTER_MULTI_F64_ROUTE     1         0: rf_filter_multi_f64 fuses every fusable query, also the shapes its measured routing rules send through rf_filter_f64 (A/B measurements)
  *   RF_JOIN                       1         0: rf_join_u32 / rf_join_f64 send every row of Q through rf_corpus_take + rf_filter_u32 / rf_filter_f64 instead of the device road (identical results; both calls read it)
- *   RF_JOIN_BATCH                 16384     most rows of Q per device batch of rf_join_u32 / rf_join_f64 (2 KiB of table scratch per row; 1 .. 1048576; both calls read it)
+ *                                           -- and rf_join_topk_u32 every row through rf_corpus_take + rf_topk_u32
+ *   RF_JOIN_BATCH                 16384     most rows of Q per device batch of rf_join_u32 / rf_join_f64 (2 KiB of table scratch per row; 1 .. 1048576; both calls read it),
+ *                                           and of rf_join_topk_u32
+ *   RF_JOIN_TOPK_UNITS            0 (auto)  units (spans of tiles of one group of four rows) a batch of rf_join_topk_u32 should make; auto: the workgroups of a launch, and no
+ *                                           span below 128 tiles.  Any other value is taken as it is (1: one unit per group; large: one tile per unit): the forced
+ *                                           several-units-per-row run of tests/join_topk_check.py and A/B measurements.  Results are identical for every value
  *   RF_JARO_PRIV                  0         1: Jaro asm kernel gathers from a conflict-free copy of the pattern table (corpora of <= 64 symbols; measured: no gain)
  *   RF_WF_REG                     1         0: LDS rows instead of register rows for generalized weights, queries <= 64
  *   RF_TRANSLATE_DIRECT           1         0: staged translation of u32 overflow symbols
@@ -647,6 +652,48 @@ rf_status rf_join_f64(rf_metric metric, const rf_corpus *queries, const uint64_t
                       uint64_t query_base, uint64_t index_base, uint64_t capacity,
                       uint64_t *out_query, uint64_t *out_index, double *out_score, uint64_t *out_count,
                       rf_join_order order, void *stream);
+
+/* ---- join, top-k: the k best candidates for every row of a packed corpus ------------------------------------
+ * "For every record of A, its best match(es) in B" (extractOne / extract(limit=k) over a whole table) with the queries themselves a packed
+ * corpus in HBM.  Q = the rows query_indices[0 .. m) of `queries`, any order, repeats allowed; NULL asks for every row and m must then equal
+ * rf_corpus_count(queries) (Q: as rf_join_u32).  Row j of the output is exactly what
+ *   rf_topk_u32(rf_comparator_new(metric, the bytes of row Q[j]), corpus, op, args, k, index_base, ...)
+ * returns: drop None, order by (score ascending for RF_OP_DISTANCE / descending for RF_OP_SIMILARITY, index ascending), keep the first k --
+ * the same tie rule, the same None rule under an OPTIONAL args->cutoff_usize, the same documented deviations (the rule: as rf_topk_u32; the
+ * rows: as rf_topk_multi_u32).  out_score and out_index are HOST arrays, row-major [m][k]; out_count[m] is a HOST array too; only the first
+ * out_count[j] entries of row j are defined (as rf_topk_multi_u32).  op is RF_OP_DISTANCE or RF_OP_SIMILARITY.  `queries` and `corpus` may
+ * be the same handle (as rf_join_u32).
+ * flags: RF_JOIN_NO_SELF -- the candidate whose local index equals the query's ROW INDEX in `queries` (not its position in Q) is never
+ * offered; both indices are taken before index_base is added (as RF_JOIN_UPPER compares).  A self-join then returns each record's k nearest
+ * OTHER records.  RF_JOIN_UPPER and every other bit are RF_ERR_INVALID_ARG here; rf_join_u32 / rf_join_f64 go on refusing every bit but
+ * RF_JOIN_UPPER.
+ * Two roads (as rf_join_u32).  On the DEVICE: both corpora hold bytes, levenshtein (uniform or Indel-like weights) / indel / lcs_seq, rows
+ * of <= 64 symbols, k <= 64, and a plan rf_topk_multi_u32 would fuse -- no early-out, i.e. no cutoff or a loose one.  Only the rows' lengths
+ * come home; tables are built on the device out of the query corpus' payload; rows are sorted by length, cut into batches (RF_JOIN_BATCH)
+ * and evaluated 4 at a time by a kernel that walks a work list and keeps four register-resident k-entry lists per lane; per batch one table
+ * build, one scan per query class that occurs and one selection launch.  The call allocates on the device, per row of a batch, 2 KiB of
+ * table and (units of the row's group) x k x 8 bytes of list segment -- the batch's units are held near the number of workgroups a launch
+ * runs, so a full batch of 16384 rows at k = 64 stays within ~25 MiB of segments -- and k x 8 bytes of keys per fused row of the CALL, which
+ * come home ONCE, after the last batch (chosen over a copy per batch: at 65536 rows x k = 64 that is 32 MiB on either side, and a copy per
+ * batch would synchronize the stream per batch); the host holds the same k x 8 bytes per row while the call runs.  PER QUERY: every other
+ * row (longer rows, k > 64, a tight cutoff, osa, damerau_levenshtein, hamming / prefix / postfix, general weight tables, a `char` corpus on
+ * either side) goes through rf_corpus_take, rf_comparator_new and rf_topk_u32, one row at a time; under RF_JOIN_NO_SELF that road asks for
+ * k + 1 entries and drops the row's own, or the last one if its own is not among them.  RF_TRACE_PLAN prints
+ * "[rf plan] join_topk: m=.. k=.. batches=.. groups=.. units=.. per_query=.."; RF_JOIN=0 sends every row per query, RF_JOIN_BATCH bounds a
+ * batch, RF_JOIN_TOPK_UNITS forces the units of a batch (results are identical for every value).
+ * Errors: a null queries / corpus / args, k == 0, an op other than the two above, an unknown or f64-valued metric (jaro, jaro_winkler, fuzz
+ * ratio), an unknown flag bit: RF_ERR_INVALID_ARG, decided before either corpus is looked at or a device is touched, nothing written.
+ * m == 0 is RF_OK and writes NOTHING, and this rule comes first (the arrays may then be NULL).  With m != 0 a null out_score, out_index or
+ * out_count is RF_ERR_INVALID_ARG.  Then: an index >= rf_corpus_count(queries), m != count with query_indices == NULL, m beyond 2^32 - 2,
+ * or corpora on different devices: RF_ERR_INVALID_ARG, nothing written.  Either corpus empty (and m != 0): RF_OK with every count 0.
+ * A call that does not return RF_OK writes nothing.
+ * Out of scope: f64 scores (an rf_join_topk_f64), an early-out variant for tight cutoffs, device-resident output, a multi-GPU form (shards
+ * are separate calls with their bases; their rows merge on the host with rf_topk_merge_u32), and a fused road for `char` corpora. */
+#define RF_JOIN_NO_SELF 2u
+rf_status rf_join_topk_u32(rf_metric metric, const rf_corpus *queries, const uint64_t *query_indices, uint64_t m,
+                           const rf_corpus *corpus, rf_op op, const rf_args *args, uint32_t flags, uint32_t k,
+                           uint64_t index_base,
+                           uint32_t *out_score, uint64_t *out_index, uint32_t *out_count, void *stream);
 
 /* ---- top-k ------------------------------------------------------------------------------------
  * The reference has no extract/top-k API; this is the engine's own reduction over the scores above,

@@ -336,6 +336,33 @@ class BatchComparator:
         cls.last_join_count = int(cnt.value)
         return oq[:have], oi[:have], sc[:have]
 
+    @classmethod
+    def join_topk(cls, queries: Corpus, corpus: Corpus, k: int, op: int = N.OP_DISTANCE, args: Optional[Args] = None, *, score_cutoff=None, query_indices=None,
+                  index_base: int = 0, no_self: bool = False, weights=None, stream=None):
+        """The k best candidates of `corpus` for every row of the packed corpus `queries` (rf_join_topk_u32): `(scores uint32 [m, k], indices uint64 [m, k],
+        counts uint32 [m])`, row j being what `cls(row j).topk(corpus, k, op, ...)` returns -- ordered by (score, index), best first; only the first counts[j]
+        entries of row j are defined.  No cutoff is needed.  `queries` and `corpus` may be the same object; `no_self=True` then never offers a row its own
+        candidate (compared by row index), so each record gets its k nearest OTHER records.  `query_indices`: the rows, any order, repeats allowed; None =
+        every row."""
+        if cls.FLOAT or op >= N.OP_NORMALIZED_DISTANCE:
+            raise ValueError("join_topk: distance or similarity of the usize metrics only")
+        k = int(k)
+        if not 0 <= k <= 0xFFFFFFFF:
+            raise ValueError("join_topk: k must fit an unsigned 32-bit integer")  # (k == 0 is the library's to refuse)
+        ca = _mk_args(args, score_cutoff, None, weights, None).to_c(False)
+        if query_indices is None:
+            qi, m = None, len(queries)
+        else:
+            qi = np.ascontiguousarray(query_indices, dtype=np.uint64)
+            m = int(qi.size)
+        scores = np.empty((m, k), dtype=np.uint32)
+        idx = np.empty((m, k), dtype=np.uint64)
+        cnt = np.zeros(m, dtype=np.uint32)
+        N.check(N.lib().rf_join_topk_u32(cls.METRIC, queries._h, qi.ctypes.data if qi is not None and m else None, m, corpus._h, op, C.byref(ca),
+                                         N.JOIN_NO_SELF if no_self else 0, k, index_base, scores.ctypes.data if m else None, idx.ctypes.data if m else None,
+                                         cnt.ctypes.data if m else None, stream))
+        return scores, idx, cnt
+
     def distance_many(self, corpus, args=None, **kw):
         return self.many(N.OP_DISTANCE, corpus, args, **kw)
 

@@ -275,6 +275,28 @@ hipError_t launch_join_pm(const JoinPmParams& p, hipStream_t stream);
 // h_items / h_prefix: the host's copies of what jp.items / jp.prefix hold, checked (join_valid) before anything is launched
 hipError_t launch_join(RawKind raw, bool narrow, const JoinParams& jp, const JoinItem* h_items, const uint32_t* h_prefix, hipStream_t stream);
 
+// rf_join_topk.hip: the k best candidates for every row of a batch (rf_join_topk_u32) over the same work list.  A member's lists -- one per unit of its item -- fill
+// its table's segment; join_topk_select_kernel reduces a segment to the row's k keys.
+struct JoinTopkParams {
+    ScanParams s;              // the scanned corpus and the finishing coefficients (plan(); an optional loose cutoff); topk_desc = similarity
+    const JoinItem* items;     // device copies of a JoinList under `span`
+    const uint32_t* prefix;
+    uint32_t n_items, n_units, span;
+    uint32_t batch;            // tables of the batch
+    const uint64_t* tables;
+    uint32_t k;                // 1..64
+    uint32_t seg_units;        // unit capacity of a segment: >= the units of every item (join_topk_seg_units)
+    uint32_t seg_cap;          // seg_units * k
+    uint32_t no_self;          // RF_JOIN_NO_SELF: the candidate whose local index is the member's row index is not offered
+    uint64_t* seg;             // [batch][seg_cap]: unit `ord` of table b's item leaves its merged list at b * seg_cap + ord * k + lane (score or ~score) << 32 | local index, ~0 = none
+    // join_topk_select_kernel
+    const uint32_t* tab_units; // [batch] units of the item table b belongs to: the segment's first tab_units[b] * k keys are that row's
+    uint64_t* keys;            // [batch][k]: the row's k best, best first, ~0 = empty
+};
+// h_items / h_prefix as in launch_join; also refuses a k or a segment the kernel cannot hold
+hipError_t launch_join_topk(RawKind raw, bool narrow, const JoinTopkParams& jp, const JoinItem* h_items, const uint32_t* h_prefix, hipStream_t stream);
+hipError_t launch_join_topk_select(const JoinTopkParams& jp, hipStream_t stream);  // one workgroup per table of the batch
+
 // kernel launchers (rf_scan.hip, rf_long.hip, rf_damerau.hip, rf_compare.hip, rf_jaro.hip, rf_pack.hip)
 hipError_t launch_scan(RawKind raw, const ScanParams& p, hipStream_t stream, int* grid_used);
 hipError_t launch_osa1_asm(const ScanParams& p, hipStream_t stream, int grid);   // the same around the OSA column (OsaState<1>)

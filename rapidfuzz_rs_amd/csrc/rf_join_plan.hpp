@@ -1,6 +1,7 @@
-// rf_join_plan.hpp -- the work list of rf_join_u32 / rf_join_f64 (rf_api_join.hip builds it, rf_join.hip join_kernel walks it): which queries of a batch share a work item,
+// rf_join_plan.hpp -- the work list of rf_join_u32 / rf_join_f64 / rf_join_topk_u32 (rf_api_join.hip builds it, rf_join.hip join_kernel and rf_join_topk.hip join_topk_kernel
+// walk it): which queries of a batch share a work item,
 // which tiles an item visits, and which workgroup unit walks which part of them.  Plain arithmetic, no HIP call: the host and the kernel compile the same
-// join_unit(), and a host-compiled test (tests/cpp/join_plan_check.cpp) checks all of it without a device.
+// join_unit(), and host-compiled tests (tests/cpp/join_plan_check.cpp, tests/cpp/join_topk_plan_check.cpp) check all of it without a device.
 //
 //   query      a fusable row of the query corpus: its length, its position in Q, its row index, and its plan's tile window [tile_begin, tile_end)
 //   batch      the queries [from, to) of the call's list SORTED by (length, position): table b of the batch belongs to query from + b
@@ -8,6 +9,9 @@
 //              windows; neighbours in length order have (nearly) the same window, so the union reads little that no member wants
 //   unit       kJoinSpan consecutive tiles of one item: what a workgroup stages the item's tables for.  prefix[i] = units before item i; unit u belongs to
 //              the item with prefix[i] <= u < prefix[i + 1] and covers tiles tile_begin + (u - prefix[i]) * span ... (+ span, clipped to tile_end)
+//   span       tiles per unit.  The joins use kJoinSpan.  rf_join_topk_u32 keeps one k-entry list per (unit, member), so it wants few, long units: its span is
+//              join_topk_span()'s -- as long as the batch still makes about as many units as the device runs workgroups -- and a member's lists fill a SEGMENT
+//              of join_topk_seg_units() x k keys, the unit with ordinal u - prefix[i] at ordinal * k
 #pragma once
 
 #include <stdint.h>
@@ -57,6 +61,24 @@ RF_JP_HD JoinUnit join_unit(const uint32_t* prefix, uint32_t n_items, const Join
     r.tile_begin = t0 < e ? (uint32_t)t0 : e;
     r.tile_end = t0 + span < e ? (uint32_t)(t0 + span) : e;
     return r;
+}
+
+// rf_join_topk_u32: the span of a batch of n_items items over a corpus of n_tiles tiles, so that the batch makes about target_units units when the work allows it:
+// every item gets target_units / n_items units (at least one), i.e. its window -- at most the whole corpus -- is cut into spans of ceil(n_tiles / that).  Never
+// below kJoinSpan (a unit pays a table stage and a list merge: 32 tiles per wavefront carry that), unless the target is FORCED (RF_JOIN_TOPK_UNITS: tests and
+// A/B measurements), when any span down to one tile is taken.
+RF_JP_HD uint32_t join_topk_span(uint32_t n_tiles, uint32_t n_items, uint32_t target_units, bool forced = false)
+{
+    const uint32_t per_item = n_items && target_units > n_items ? target_units / n_items : 1u;
+    uint32_t span = n_tiles / per_item + (n_tiles % per_item != 0);
+    if (span == 0) span = 1;
+    return forced || span >= kJoinSpan ? span : kJoinSpan;
+}
+// ... and the most units any item has under that span (its window is at most [0, n_tiles)): the unit capacity of a member's segment.  At least 1.
+RF_JP_HD uint32_t join_topk_seg_units(uint32_t n_tiles, uint32_t span)
+{
+    const uint32_t u = join_units_of(0, n_tiles, span);
+    return u ? u : 1u;
 }
 
 }  // namespace rf

@@ -152,6 +152,26 @@ impl Corpus {
         let have = (n as usize).min(cap);
         Ok((0..have).map(|t| (q[t], idx[t], val[t])).collect())
     }
+    /// The k best candidates of `self` for every row of `queries` (rf_join_topk_u32): row j holds the (index_base + candidate, score) pairs of row
+    /// `query_indices[j]` (`None` = every row), best first by (score, candidate) -- ascending scores for `RF_OP_DISTANCE`, descending for `RF_OP_SIMILARITY` -- at
+    /// most `k` of them.  `args` may carry a cutoff and need not.  `no_self`: a row is never offered the candidate with its own row index, so a self-join
+    /// (`queries` is `self`) returns each record's k nearest other records.
+    #[allow(clippy::too_many_arguments)]
+    pub fn join_topk(&self, queries: &Corpus, metric: std::os::raw::c_int, op: std::os::raw::c_int, args: &RfArgs, k: u32, query_indices: Option<&[u64]>, no_self: bool,
+                     index_base: u64) -> Result<Vec<Vec<(u64, usize)>>, Error> {
+        let (qi, m) = match query_indices {
+            Some(v) if v.is_empty() => return Ok(Vec::new()),
+            Some(v) => (v.as_ptr(), v.len()),
+            None => (std::ptr::null(), queries.len()),
+        };
+        let flags = if no_self { RF_JOIN_NO_SELF } else { 0 };
+        let kk = k as usize;
+        let (mut score, mut idx, mut count) = (vec![0u32; m * kk], vec![0u64; m * kk], vec![0u32; m]);
+        check(unsafe {
+            rf_join_topk_u32(metric, queries.0, qi, m as u64, self.0, op, args, flags, k, index_base, score.as_mut_ptr(), idx.as_mut_ptr(), count.as_mut_ptr(), std::ptr::null_mut())
+        })?;
+        Ok((0..m).map(|j| (0..count[j] as usize).map(|t| (idx[j * kk + t], score[j * kk + t] as usize)).collect()).collect())
+    }
     /// The same as `String`s, for a corpus of `char`s (a byte corpus reads as Latin-1: its bytes are the code points 0..255).
     pub fn take_chars(&self, indices: &[u64], index_base: u64) -> Result<Vec<String>, Error> {
         if indices.is_empty() {
