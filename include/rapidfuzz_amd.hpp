@@ -344,19 +344,34 @@ public:
     // ---- the k best candidates of `c` for every row of the packed corpus `queries`, one call (rf_join_topk_u32): res[j] = (index_base + index, score) pairs of row
     // query_indices[j] (nullptr = every row; an empty list: no row) -- what distance_topk_multi of a comparator over that row returns, ordered by (score ascending,
     // index ascending), at most k of them.  No cutoff is needed.  `queries` and `c` may be the same corpus; `no_self` then never offers a row its own candidate
-    // (compared by row index), so every record gets its k nearest OTHER records.  usize metrics only.
-    static std::vector<std::vector<std::pair<uint64_t, size_t>>> distance_join_topk(const Corpus& queries, const Corpus& c, uint32_t k, const Args<usize_result>& a = {},
-                                                                                     bool no_self = false, const std::vector<uint64_t>* query_indices = nullptr,
-                                                                                     uint64_t index_base = 0)
+    // (compared by row index), so every record gets its k nearest OTHER records.  The usize metrics' pairs carry a size_t (rf_join_topk_u32); jaro / jaro_winkler's,
+    // and every normalized_*_join_topk's, a double (rf_join_topk_f64).
+    static std::vector<std::vector<std::pair<uint64_t, usize_result>>> distance_join_topk(const Corpus& queries, const Corpus& c, uint32_t k, const Args<usize_result>& a = {},
+                                                                                           bool no_self = false, const std::vector<uint64_t>* query_indices = nullptr,
+                                                                                           uint64_t index_base = 0)
     {
-        return join_topk(queries, c, k, RF_OP_DISTANCE, a.to_c(), no_self, query_indices, index_base);
+        return join_topk<usize_result>(queries, c, k, RF_OP_DISTANCE, a.to_c(), no_self, query_indices, index_base);
     }
     /// the same by similarity: (score descending, index ascending)
-    static std::vector<std::vector<std::pair<uint64_t, size_t>>> similarity_join_topk(const Corpus& queries, const Corpus& c, uint32_t k, const Args<usize_result>& a = {},
-                                                                                       bool no_self = false, const std::vector<uint64_t>* query_indices = nullptr,
-                                                                                       uint64_t index_base = 0)
+    static std::vector<std::vector<std::pair<uint64_t, usize_result>>> similarity_join_topk(const Corpus& queries, const Corpus& c, uint32_t k, const Args<usize_result>& a = {},
+                                                                                             bool no_self = false, const std::vector<uint64_t>* query_indices = nullptr,
+                                                                                             uint64_t index_base = 0)
     {
-        return join_topk(queries, c, k, RF_OP_SIMILARITY, a.to_c(), no_self, query_indices, index_base);
+        return join_topk<usize_result>(queries, c, k, RF_OP_SIMILARITY, a.to_c(), no_self, query_indices, index_base);
+    }
+    // ---- the same by normalized score (rf_join_topk_f64): "each record's best matches by normalized_similarity" -- bit for bit the doubles, and the order, of
+    // normalized_*_topk_multi of comparators over the same rows.  Over a ragged corpus this ranking differs from distance_join_topk's.
+    static std::vector<std::vector<std::pair<uint64_t, double>>> normalized_distance_join_topk(const Corpus& queries, const Corpus& c, uint32_t k, const Args<double>& a = {},
+                                                                                                bool no_self = false, const std::vector<uint64_t>* query_indices = nullptr,
+                                                                                                uint64_t index_base = 0)
+    {
+        return join_topk<double>(queries, c, k, RF_OP_NORMALIZED_DISTANCE, a.to_c(), no_self, query_indices, index_base);
+    }
+    static std::vector<std::vector<std::pair<uint64_t, double>>> normalized_similarity_join_topk(const Corpus& queries, const Corpus& c, uint32_t k, const Args<double>& a = {},
+                                                                                                  bool no_self = false, const std::vector<uint64_t>* query_indices = nullptr,
+                                                                                                  uint64_t index_base = 0)
+    {
+        return join_topk<double>(queries, c, k, RF_OP_NORMALIZED_SIMILARITY, a.to_c(), no_self, query_indices, index_base);
     }
 
     // ---- the reference's per-candidate methods (a one-candidate corpus through the same kernels)
@@ -463,19 +478,28 @@ private:
             return res;
         }
     }
-    static std::vector<std::vector<std::pair<uint64_t, size_t>>> join_topk(const Corpus& queries, const Corpus& c, uint32_t k, rf_op op, const rf_args& a, bool no_self,
-                                                                           const std::vector<uint64_t>* query_indices, uint64_t index_base)
+    // (every *_join_topk: Value picks the call -- size_t rf_join_topk_u32, double rf_join_topk_f64)
+    template <class Value>
+    static std::vector<std::vector<std::pair<uint64_t, Value>>> join_topk(const Corpus& queries, const Corpus& c, uint32_t k, rf_op op, const rf_args& a, bool no_self,
+                                                                          const std::vector<uint64_t>* query_indices, uint64_t index_base)
     {
-        static_assert(!FloatMetric, "rf_join_topk_u32 serves the usize-valued metrics");
+        constexpr bool f64 = std::is_floating_point_v<Value>;
+        static_assert(f64 || !FloatMetric, "rf_join_topk_u32 serves the usize-valued metrics");
+        using Score = std::conditional_t<f64, double, uint32_t>;
         if (query_indices && query_indices->empty()) return {};  // (an empty selection is no row; only a null pointer asks for every row)
         const uint64_t* qi = query_indices ? query_indices->data() : nullptr;
         const uint64_t m = query_indices ? query_indices->size() : queries.size();
-        std::vector<uint32_t> score(m * k), count(m);
+        const uint32_t flags = no_self ? RF_JOIN_NO_SELF : 0u;
+        std::vector<Score> score(m * k);
+        std::vector<uint32_t> count(m);
         std::vector<uint64_t> index(m * k);
-        check(rf_join_topk_u32(M, queries.handle(), qi, m, c.handle(), op, &a, no_self ? RF_JOIN_NO_SELF : 0u, k, index_base, score.data(), index.data(), count.data(), nullptr));
-        std::vector<std::vector<std::pair<uint64_t, size_t>>> res(m);
+        if constexpr (f64)
+            check(rf_join_topk_f64(M, queries.handle(), qi, m, c.handle(), op, &a, flags, k, index_base, score.data(), index.data(), count.data(), nullptr));
+        else
+            check(rf_join_topk_u32(M, queries.handle(), qi, m, c.handle(), op, &a, flags, k, index_base, score.data(), index.data(), count.data(), nullptr));
+        std::vector<std::vector<std::pair<uint64_t, Value>>> res(m);
         for (size_t j = 0; j < m; ++j)
-            for (uint32_t t = 0; t < count[j]; ++t) res[j].emplace_back(index[j * k + t], (size_t)score[j * k + t]);
+            for (uint32_t t = 0; t < count[j]; ++t) res[j].emplace_back(index[j * k + t], (Value)score[j * k + t]);
         return res;
     }
     // (every *_join: Triple picks the call -- JoinTriple rf_join_u32, JoinTripleF64 rf_join_f64)
@@ -631,6 +655,19 @@ public:
                                                                  uint64_t query_base = 0, uint64_t index_base = 0)
     {
         return detail::BatchComparator<RF_FUZZ_RATIO, true>::normalized_similarity_join(queries, c, a, upper, order, query_indices, query_base, index_base);
+    }
+    /// the k best candidates of `c` by ratio for every row of the packed corpus `queries`, one call (rf_join_topk_f64); see BatchComparator::distance_join_topk
+    static std::vector<std::vector<std::pair<uint64_t, double>>> similarity_join_topk(const Corpus& queries, const Corpus& c, uint32_t k, const detail::Args<double>& a = {},
+                                                                                       bool no_self = false, const std::vector<uint64_t>* query_indices = nullptr,
+                                                                                       uint64_t index_base = 0)
+    {
+        return detail::BatchComparator<RF_FUZZ_RATIO, true>::similarity_join_topk(queries, c, k, a, no_self, query_indices, index_base);
+    }
+    static std::vector<std::vector<std::pair<uint64_t, double>>> normalized_similarity_join_topk(const Corpus& queries, const Corpus& c, uint32_t k, const detail::Args<double>& a = {},
+                                                                                                  bool no_self = false, const std::vector<uint64_t>* query_indices = nullptr,
+                                                                                                  uint64_t index_base = 0)
+    {
+        return detail::BatchComparator<RF_FUZZ_RATIO, true>::normalized_similarity_join_topk(queries, c, k, a, no_self, query_indices, index_base);
     }
 
 private:

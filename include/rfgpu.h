@@ -74,10 +74,10 @@
  *   RF_FILTER_MULTI               1         0: rf_filter_multi_u32 / _f64 send every query through rf_filter_u32 / _f64 instead of fusing tight-cutoff queries 4 (or 2) to a pass over the corpus
  *   RF_FILTER_MULTI_F64_ROUTE     1         0: rf_filter_multi_f64 fuses every fusable query, also the shapes its measured routing rules send through rf_filter_f64 (A/B measurements)
  *   RF_JOIN                       1         0: rf_join_u32 / rf_join_f64 send every row of Q through rf_corpus_take + rf_filter_u32 / rf_filter_f64 instead of the device road (identical results; both calls read it)
- *                                           -- and rf_join_topk_u32 every row through rf_corpus_take + rf_topk_u32
+ *                                           -- and rf_join_topk_u32 / rf_join_topk_f64 every row through rf_corpus_take + rf_topk_u32 / rf_topk_f64
  *   RF_JOIN_BATCH                 16384     most rows of Q per device batch of rf_join_u32 / rf_join_f64 (2 KiB of table scratch per row; 1 .. 1048576; both calls read it),
- *                                           and of rf_join_topk_u32
- *   RF_JOIN_TOPK_UNITS            0 (auto)  units (spans of tiles of one group of four rows) a batch of rf_join_topk_u32 should make; auto: the workgroups of a launch, and no
+ *                                           and of rf_join_topk_u32 / rf_join_topk_f64
+ *   RF_JOIN_TOPK_UNITS            0 (auto)  units (spans of tiles of one group of four rows) a batch of rf_join_topk_u32 / rf_join_topk_f64 should make; auto: the workgroups of a launch, and no
  *                                           span below 128 tiles.  Any other value is taken as it is (1: one unit per group; large: one tile per unit): the forced
  *                                           several-units-per-row run of tests/join_topk_check.py and A/B measurements.  Results are identical for every value
  *   RF_JARO_PRIV                  0         1: Jaro asm kernel gathers from a conflict-free copy of the pattern table (corpora of <= 64 symbols; measured: no gain)
@@ -687,13 +687,54 @@ rf_status rf_join_f64(rf_metric metric, const rf_corpus *queries, const uint64_t
  * out_count is RF_ERR_INVALID_ARG.  Then: an index >= rf_corpus_count(queries), m != count with query_indices == NULL, m beyond 2^32 - 2,
  * or corpora on different devices: RF_ERR_INVALID_ARG, nothing written.  Either corpus empty (and m != 0): RF_OK with every count 0.
  * A call that does not return RF_OK writes nothing.
- * Out of scope: f64 scores (an rf_join_topk_f64), an early-out variant for tight cutoffs, device-resident output, a multi-GPU form (shards
+ * (By f64 score -- normalized_*, fuzz ratio, jaro / jaro_winkler: rf_join_topk_f64 below.)
+ * Out of scope: an early-out variant for tight cutoffs, device-resident output, a multi-GPU form (shards
  * are separate calls with their bases; their rows merge on the host with rf_topk_merge_u32), and a fused road for `char` corpora. */
 #define RF_JOIN_NO_SELF 2u
 rf_status rf_join_topk_u32(rf_metric metric, const rf_corpus *queries, const uint64_t *query_indices, uint64_t m,
                            const rf_corpus *corpus, rf_op op, const rf_args *args, uint32_t flags, uint32_t k,
                            uint64_t index_base,
                            uint32_t *out_score, uint64_t *out_index, uint32_t *out_count, void *stream);
+
+/* ---- join, top-k by f64 score: every row's k best candidates by normalized score ------------------------------
+ * "Each record's best match by fuzz::ratio / normalized_similarity" -- record linkage without a cutoff.  Over a ragged corpus this is NOT the
+ * u32 call's ranking: 3 edits against a 6-byte candidate are not 3 edits against a 60-byte one.  rf_join_topk_u32's contract, word for word,
+ * wherever it does not concern the score type: Q and query_indices (any order, repeats, NULL = every row), the same handle on both sides, HOST
+ * outputs [m][k] / [m] of which only the first out_count[j] entries of row j are defined, RF_JOIN_NO_SELF on the row index before the base is
+ * added and every other bit refused, m == 0 first and writing nothing, a call that does not return RF_OK writing nothing: all as above.
+ * Row j is exactly what
+ *   rf_topk_f64(rf_comparator_new(metric, the bytes of row Q[j]), corpus, op, args, k, index_base, ...)
+ * returns: the same doubles bit for bit, in the same (score, index) order, best first, with the same None rule under an OPTIONAL
+ * args->cutoff_f64 (NaN = no cutoff).  Accepted (metric, op) pairs are rf_join_f64's and rf_topk_multi_f64's: RF_OP_NORMALIZED_DISTANCE /
+ * RF_OP_NORMALIZED_SIMILARITY of the usize metrics, RF_FUZZ_RATIO with its two similarity ops (with and without
+ * RF_FLAG_RATIO_INDEL_NORMALIZATION), every op of RF_JARO / RF_JARO_WINKLER.
+ * Two roads, the u32 call's.  On the DEVICE: both corpora hold bytes, levenshtein (uniform or Indel-like weights) / indel / lcs_seq / fuzz
+ * ratio, rows of <= 64 symbols, k <= 64, a plan rf_topk_multi_f64 would fuse -- no early-out, i.e. no cutoff or a loose one -- and every
+ * maximum of the row's scan within 65535: the in-scan lists order by the 32-bit image norm_key(dist, maximum) of the normalized distance
+ * (exact and order-preserving up to there; both ops rank by ascending key, equal ratios of different fractions -- 2/4 and 4/8 -- get one
+ * key and tie by index).  That last condition is PER ROW, because the maximum grows with the row's length: over one corpus shorter rows
+ * may fuse while longer ones do not (indel, a longest candidate of 65472 bytes: rows of <= 63 symbols fuse, rows of 64 go per query).  The
+ * batches, the work list, RF_JOIN_BATCH, RF_JOIN_TOPK_UNITS, the segments and the selection launch are the u32 call's, the kernel is its
+ * normalized instantiation; the keys come home ONCE, after the last batch, and the host turns each back into its reduced fraction a / b:
+ * (double)a / (double)b is the double the single-query kernels divide out of dist and maximum, returned as it is for
+ * RF_OP_NORMALIZED_DISTANCE of a metric that is not fuzz ratio and as 1.0 - that otherwise.  PER QUERY: every other row (jaro,
+ * jaro_winkler, osa, damerau_levenshtein, hamming / prefix / postfix, general weight tables, rows beyond 64 symbols, k > 64, a tight cutoff, a
+ * maximum beyond 65535, a `char` corpus on either side) goes through rf_corpus_take, rf_comparator_new and rf_topk_f64, one row at a time;
+ * under RF_JOIN_NO_SELF that road asks for k + 1 entries and drops the row's own, or the last one if its own is not among them.  Slow by
+ * design, but no shape becomes an empty answer.  RF_TRACE_PLAN prints
+ * "[rf plan] join_topk_f64: m=.. k=.. batches=.. groups=.. units=.. per_query=.."; RF_JOIN=0, RF_JOIN_BATCH and RF_JOIN_TOPK_UNITS act as
+ * above.
+ * Errors: a null queries / corpus / args, k == 0, RF_OP_DISTANCE / RF_OP_SIMILARITY of a usize metric (u32-valued: rf_join_topk_u32), a
+ * distance op of fuzz ratio, an unknown metric, op or flag bit: RF_ERR_INVALID_ARG, decided before either corpus is looked at or a device is
+ * touched, nothing written.  Then, as above: m == 0 is RF_OK and writes nothing; a null output with m != 0, an index out of range, m != count
+ * with query_indices == NULL, m beyond 2^32 - 2, corpora on different devices: RF_ERR_INVALID_ARG; either corpus empty: RF_OK with every
+ * count 0.
+ * Out of scope: a wider key for maxima beyond 65535, an early-out variant for tight cutoffs, device-resident output, a multi-GPU form
+ * (shards are separate calls with their bases; their rows merge on the host), and a fused road for `char` corpora. */
+rf_status rf_join_topk_f64(rf_metric metric, const rf_corpus *queries, const uint64_t *query_indices, uint64_t m,
+                           const rf_corpus *corpus, rf_op op, const rf_args *args, uint32_t flags, uint32_t k,
+                           uint64_t index_base,
+                           double *out_score, uint64_t *out_index, uint32_t *out_count, void *stream);
 
 /* ---- top-k ------------------------------------------------------------------------------------
  * The reference has no extract/top-k API; this is the engine's own reduction over the scores above,

@@ -346,21 +346,40 @@ class BatchComparator:
         every row."""
         if cls.FLOAT or op >= N.OP_NORMALIZED_DISTANCE:
             raise ValueError("join_topk: distance or similarity of the usize metrics only")
+        return cls._join_topk(False, queries, corpus, k, op, _mk_args(args, score_cutoff, None, weights, None), query_indices, index_base, no_self, stream)
+
+    @classmethod
+    def join_topk_f64(cls, queries: Corpus, corpus: Corpus, k: int, op: Optional[int] = None, args: Optional[Args] = None, *, score_cutoff=None, query_indices=None,
+                      index_base: int = 0, no_self: bool = False, weights=None, prefix_weight=None, stream=None):
+        """`join_topk` by f64 score (rf_join_topk_f64): `(scores float64 [m, k], indices uint64 [m, k], counts uint32 [m])`, row j holding exactly the doubles
+        `cls(row j).topk(corpus, k, op, ...)` returns, in the same (score, index) order.  op: normalized_distance / normalized_similarity (the default) of the
+        usize metrics, similarity (the default) / normalized_similarity of `fuzz.RatioBatchComparator`, any op of jaro / jaro_winkler (default: similarity).
+        "Each record's best match by ratio": over a ragged corpus this ranking differs from `join_topk`'s.  Every other argument is `join_topk`'s."""
+        if op is None:
+            op = N.OP_SIMILARITY if cls.FLOAT else N.OP_NORMALIZED_SIMILARITY
+        if not cls.FLOAT and op < N.OP_NORMALIZED_DISTANCE:
+            raise ValueError("join_topk_f64: distance and similarity of the usize metrics are uint32-valued (join_topk)")
+        return cls._join_topk(True, queries, corpus, k, op, _mk_args(args, score_cutoff, None, weights, prefix_weight), query_indices, index_base, no_self, stream)
+
+    @classmethod
+    def _join_topk(cls, is_f: bool, queries: Corpus, corpus: Corpus, k: int, op: int, a: Args, query_indices, index_base, no_self, stream):
+        """what `join_topk` and `join_topk_f64` share"""
+        name = "join_topk_f64" if is_f else "join_topk"
         k = int(k)
         if not 0 <= k <= 0xFFFFFFFF:
-            raise ValueError("join_topk: k must fit an unsigned 32-bit integer")  # (k == 0 is the library's to refuse)
-        ca = _mk_args(args, score_cutoff, None, weights, None).to_c(False)
+            raise ValueError(f"{name}: k must fit an unsigned 32-bit integer")  # (k == 0 is the library's to refuse)
+        ca = a.to_c(is_f)
         if query_indices is None:
             qi, m = None, len(queries)
         else:
             qi = np.ascontiguousarray(query_indices, dtype=np.uint64)
             m = int(qi.size)
-        scores = np.empty((m, k), dtype=np.uint32)
+        scores = np.empty((m, k), dtype=np.float64 if is_f else np.uint32)
         idx = np.empty((m, k), dtype=np.uint64)
         cnt = np.zeros(m, dtype=np.uint32)
-        N.check(N.lib().rf_join_topk_u32(cls.METRIC, queries._h, qi.ctypes.data if qi is not None and m else None, m, corpus._h, op, C.byref(ca),
-                                         N.JOIN_NO_SELF if no_self else 0, k, index_base, scores.ctypes.data if m else None, idx.ctypes.data if m else None,
-                                         cnt.ctypes.data if m else None, stream))
+        fn = N.lib().rf_join_topk_f64 if is_f else N.lib().rf_join_topk_u32
+        N.check(fn(cls.METRIC, queries._h, qi.ctypes.data if qi is not None and m else None, m, corpus._h, op, C.byref(ca), N.JOIN_NO_SELF if no_self else 0, k,
+                   index_base, scores.ctypes.data if m else None, idx.ctypes.data if m else None, cnt.ctypes.data if m else None, stream))
         return scores, idx, cnt
 
     def distance_many(self, corpus, args=None, **kw):

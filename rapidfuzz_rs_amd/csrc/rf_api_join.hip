@@ -18,6 +18,10 @@
 // road takes the rows whose plan rf_topk_multi_u32 would fuse -- no early-out: no cutoff or a loose one -- at k <= 64: per batch the tables, one join_topk_kernel per
 // class that occurs (rf_join_topk.hip) under the batch's span (join_topk_span) and one selection launch; the keys come home once, after the last batch.
 // Its per-query road is rf_topk_u32.
+// rf_join_topk_f64 is the same body (join_topk_call<double>; JoinTopkScore<Score> holds what differs): the normalized ops, fuzz ratio, jaro / jaro_winkler.  Its device
+// road takes what rf_topk_multi_f64 would fuse -- f64 plans without an early-out whose every maximum stays within the 32-bit score image, norm_key_fits per ROW with the
+// corpus' longest candidate -- through join_topk_kernel's kNorm instantiation; the keys are decoded by decode_norm_keys (rf_host.hpp), the function rf_topk_multi_f64 uses.
+// Its per-query road is rf_topk_f64.
 // Product code: never includes or links anything from oracle/.
 #include <numeric>
 
@@ -327,8 +331,9 @@ rf_status check_join_args(const char* fn, bool f64, rf_metric metric, const rf_c
     if (f64 ? std::isnan(args_in->cutoff_f64) : args_in->cutoff_usize == RF_NO_CUTOFF) return bad("args must carry a score_cutoff (without one the answer is every pair)");
     return RF_OK;
 }
-// ... and of rf_join_topk_u32: no cutoff is required, k is, and the flag it knows is RF_JOIN_NO_SELF
-rf_status check_join_topk_args(const char* fn, rf_metric metric, const rf_corpus* queries, const rf_corpus* corpus, rf_op op, const rf_args* args_in, uint32_t flags, uint32_t k)
+// ... and of rf_join_topk_u32 / rf_join_topk_f64: no cutoff is required, k is, and the flag they know is RF_JOIN_NO_SELF
+rf_status check_join_topk_args(const char* fn, bool f64, rf_metric metric, const rf_corpus* queries, const rf_corpus* corpus, rf_op op, const rf_args* args_in, uint32_t flags,
+                               uint32_t k)
 {
     const std::string name(fn);
     auto bad = [&](const std::string& why) {
@@ -337,7 +342,7 @@ rf_status check_join_topk_args(const char* fn, rf_metric metric, const rf_corpus
     };
     if (!queries || !corpus || !args_in) return bad("null handle or args");
     if (k == 0) return bad("k must be at least 1");
-    return check_join_metric_op(name, false, metric, op, flags, RF_JOIN_NO_SELF);
+    return check_join_metric_op(name, f64, metric, op, flags, RF_JOIN_NO_SELF);
 }
 
 // Q: the row index of every position, after the checks that look at the query corpus (nothing is written before them)
@@ -513,15 +518,43 @@ rf_status join_call(rf_metric metric, const rf_corpus* queries, const uint64_t* 
     return RF_OK;
 }
 
-// ---- rf_join_topk_u32
+// ---- rf_join_topk_u32 / rf_join_topk_f64
+// what the two score types do not share: the entry point's name and trace prefix, whether plan() is asked for f64 (and the kernel for its normalized instantiation),
+// which rf_topk_* the per-query road calls
+template <class Score>
+struct JoinTopkScore;
+template <>
+struct JoinTopkScore<uint32_t> {
+    static constexpr bool kF64 = false;
+    static constexpr const char* kName = "rf_join_topk_u32";
+    static constexpr const char* kTrace = "join_topk";
+    static rf_status topk(const rf_comparator* c, const rf_corpus* corpus, rf_op op, const rf_args* args, uint32_t ask, uint32_t* score, uint64_t* index, uint32_t* count, void* stream)
+    {
+        return rf_topk_u32(c, corpus, op, args, ask, 0, score, index, count, nullptr, RF_MEM_HOST, stream);
+    }
+};
+template <>
+struct JoinTopkScore<double> {
+    static constexpr bool kF64 = true;
+    static constexpr const char* kName = "rf_join_topk_f64";
+    static constexpr const char* kTrace = "join_topk_f64";
+    static rf_status topk(const rf_comparator* c, const rf_corpus* corpus, rf_op op, const rf_args* args, uint32_t ask, double* score, uint64_t* index, uint32_t* count, void* stream)
+    {
+        uint64_t n = 0;
+        const rf_status s = rf_topk_f64(c, corpus, op, args, ask, 0, score, index, &n, nullptr, RF_MEM_HOST, stream);
+        *count = (uint32_t)n;
+        return s;
+    }
+};
+
 // The device road over the rows `fused` (sorted): row i of `keys` ([fused.size()][k], best first, ~0 = empty) belongs to fused[i].  Per batch: the span for its
 // items (join_topk_span), the work lists, the tables, the batch's segments filled with ~0, one join_topk_kernel per class that occurs, one selection launch into the
-// batch's rows of the call's key buffer.  The keys come home once, after the last batch.
-rf_status join_topk_device(RawKind raw, const ScanParams& plan0, const rf_corpus* queries, const rf_corpus* corpus, const std::vector<JoinQuery>& fused, const uint32_t* d_row_slot,
-                           const uint32_t* d_row_len, rf_op op, uint32_t flags, uint32_t k, ScratchSet& sc, hipStream_t st, std::vector<uint64_t>* keys, uint32_t* n_batches,
-                           uint32_t* n_groups, uint64_t* n_units)
+// batch's rows of the call's key buffer.  The keys come home once, after the last batch.  `norm` (rf_join_topk_f64): plan0 is an f64 plan of a normalized op and the keys
+// are norm_key images (the kernel's kNorm instantiation).
+rf_status join_topk_device(const char* kName, bool norm, RawKind raw, const ScanParams& plan0, const rf_corpus* queries, const rf_corpus* corpus, const std::vector<JoinQuery>& fused,
+                           const uint32_t* d_row_slot, const uint32_t* d_row_len, rf_op op, uint32_t flags, uint32_t k, ScratchSet& sc, hipStream_t st, std::vector<uint64_t>* keys,
+                           uint32_t* n_batches, uint32_t* n_groups, uint64_t* n_units)
 {
-    static constexpr const char* kName = "rf_join_topk_u32";
     JoinBatches jb;
     if (const rf_status s = jb.init(queries, corpus, fused.size(), d_row_slot, d_row_len, 1, sc, st); s != RF_OK) return s;
     const uint32_t n_tiles = corpus->n_tiles;
@@ -550,7 +583,8 @@ rf_status join_topk_device(RawKind raw, const ScanParams& plan0, const rf_corpus
     JoinTopkParams jp{};
     jp.s = plan0;
     jp.s.out = nullptr, jp.s.early = 0, jp.s.prefill_none = 0, jp.s.tile_step = 1, jp.s.len1 = 0, jp.s.tile_begin = 0, jp.s.tile_end = 0;
-    jp.s.topk_k = k, jp.s.topk_desc = op == RF_OP_SIMILARITY, jp.s.key_index_base = 0;  // (index_base is added on the host, in 64 bits)
+    jp.s.topk_k = k, jp.s.topk_desc = op == RF_OP_SIMILARITY, jp.s.key_index_base = 0;  // (index_base is added on the host, in 64 bits; topk_desc is not read under norm)
+    jp.norm = norm ? 1u : 0u;
     jp.tables = jb.d_tables;
     jp.k = k;
     jp.no_self = (flags & RF_JOIN_NO_SELF) ? 1u : 0u;
@@ -596,24 +630,26 @@ rf_status join_topk_device(RawKind raw, const ScanParams& plan0, const rf_corpus
 }
 
 // One row of the answer before the bases: local indices, best first
+template <class Score>
 struct TopkRow {
-    std::vector<uint32_t> score;
+    std::vector<Score> score;
     std::vector<uint64_t> index;
 };
-// the per-query road over the positions `rest` of Q: rf_topk_u32 of every row.  RF_JOIN_NO_SELF: k + 1 are asked for and the entry of the row's own index is
-// dropped, or the last one if it is not among them
+// the per-query road over the positions `rest` of Q: rf_topk_u32 / rf_topk_f64 of every row.  RF_JOIN_NO_SELF: k + 1 are asked for and the entry of the row's own
+// index is dropped, or the last one if it is not among them
+template <class Score>
 rf_status join_topk_per_query(rf_metric metric, const rf_corpus* queries, const std::vector<uint32_t>& qidx, const std::vector<uint32_t>& rest, const rf_corpus* corpus, rf_op op,
-                              const rf_args* args, uint32_t flags, uint32_t k, void* stream, std::vector<TopkRow>* rows)
+                              const rf_args* args, uint32_t flags, uint32_t k, void* stream, std::vector<TopkRow<Score>>* rows)
 {
     const bool no_self = (flags & RF_JOIN_NO_SELF) != 0;
     const uint32_t ask = (uint32_t)std::min<uint64_t>((uint64_t)k + (no_self ? 1 : 0), std::max<uint64_t>(corpus->n, 1));  // (a row has at most n entries)
-    std::vector<uint32_t> score(ask);
+    std::vector<Score> score(ask);
     std::vector<uint64_t> index(ask);
     return for_each_row_comparator(metric, queries, qidx, rest, stream, [&](uint32_t pos, const rf_comparator* c) {
         uint32_t count = 0;
-        const rf_status s = rf_topk_u32(c, corpus, op, args, ask, 0, score.data(), index.data(), &count, nullptr, RF_MEM_HOST, stream);
+        const rf_status s = JoinTopkScore<Score>::topk(c, corpus, op, args, ask, score.data(), index.data(), &count, stream);
         if (s != RF_OK) return s;
-        TopkRow& r = (*rows)[pos];
+        TopkRow<Score>& r = (*rows)[pos];
         for (uint32_t i = 0; i < count; ++i) {
             if (no_self && index[i] == qidx[pos]) continue;
             if (r.score.size() == k) break;
@@ -623,11 +659,13 @@ rf_status join_topk_per_query(rf_metric metric, const rf_corpus* queries, const 
     });
 }
 
+template <class Score>
 rf_status join_topk_call(rf_metric metric, const rf_corpus* queries, const uint64_t* query_indices, uint64_t m, const rf_corpus* corpus, rf_op op, const rf_args* args_in, uint32_t flags,
-                         uint32_t k, uint64_t index_base, uint32_t* out_score, uint64_t* out_index, uint32_t* out_count, void* stream)
+                         uint32_t k, uint64_t index_base, Score* out_score, uint64_t* out_index, uint32_t* out_count, void* stream)
 {
-    static constexpr const char* kName = "rf_join_topk_u32";
-    if (const rf_status s = check_join_topk_args(kName, metric, queries, corpus, op, args_in, flags, k); s != RF_OK) return s;
+    using JS = JoinTopkScore<Score>;
+    static constexpr const char* kName = JS::kName;
+    if (const rf_status s = check_join_topk_args(kName, JS::kF64, metric, queries, corpus, op, args_in, flags, k); s != RF_OK) return s;
     if (m == 0) return RF_OK;  // (writes nothing)
     if (!out_score || !out_index || !out_count) {
         set_error(std::string(kName) + ": null output");
@@ -654,7 +692,7 @@ rf_status join_topk_call(rf_metric metric, const rf_corpus* queries, const uint6
     std::vector<uint32_t> rest;  // positions of Q for the per-query road
     uint32_t n_batches = 0, n_groups = 0;
     uint64_t n_units = 0;
-    const bool device_metric = metric == RF_LEVENSHTEIN || metric == RF_INDEL || metric == RF_LCS_SEQ;
+    const bool device_metric = metric == RF_LEVENSHTEIN || metric == RF_INDEL || metric == RF_LCS_SEQ || (JS::kF64 && metric == RF_FUZZ_RATIO);
     if (sw_join() && device_metric && !queries->wide && !corpus->wide && k <= (uint32_t)kWave) {
         DeviceGuard guard(corpus->device);
         if (!guard.ok) {
@@ -665,21 +703,26 @@ rf_status join_topk_call(rf_metric metric, const rf_corpus* queries, const uint6
         TakeParams tp;
         std::vector<uint32_t> lens;
         if (const rf_status s = join_lengths(kName, queries, qidx, sc, st, &tp, &lens); s != RF_OK) return s;
-        // (what rf_topk_multi_u32 fuses: no early-out -- no cutoff or a loose one -- and one kernel family, finishing and factor for the whole launch)
-        // ASSUMPTION: for these three metrics finish, factor and op follow from the metric, the weights and the op -- not from the row's length -- so the first
-        // accepted length's key is every accepted length's.  Should a length ever plan to another key, its rows are still answered (per query, counted in the plan
-        // line's per_query); if that length could be the common one, pick the majority key here instead of the first.
+        // (what rf_topk_multi_u32 / rf_topk_multi_f64 fuse: no early-out -- no cutoff or a loose one -- and one kernel family, finishing and factor for the whole
+        // launch; by f64 score also norm_key_fits, PER ROW: the maximum grows with the row's length, so over one corpus shorter rows may fuse while longer ones go
+        // per query)
+        // ASSUMPTION: for these metrics (the fuzz ratio is its inner metric's normalized similarity in plan()) finish, factor and op follow from the metric, the
+        // weights and the op -- not from the row's length -- so the first accepted length's key is every accepted length's.  Should a length ever plan to another
+        // key, its rows are still answered (per query, counted in the plan line's per_query); if that length could be the common one, pick the majority key here
+        // instead of the first.
         bool have_first = false;
         MultiGroupKey first{};
         auto fusable = [&](const ScanParams& p, RawKind raw) {
-            if (p.early || p.out_f64) return false;
+            if (p.early || (p.out_f64 != 0) != JS::kF64) return false;
+            if (JS::kF64 && !norm_key_fits(p.fin_mS, p.fin_mM, p.len1, corpus->max_len)) return false;
             const MultiGroupKey key{raw, p.finish, p.factor, p.op, false};
             if (!have_first) first = key, have_first = true;
             return key == first;
         };
-        if (const rf_status s = join_plan_rows(metric, corpus, op, args, false, qidx, lens, fusable, &pl, &rest); s != RF_OK) return s;
+        if (const rf_status s = join_plan_rows(metric, corpus, op, args, JS::kF64, qidx, lens, fusable, &pl, &rest); s != RF_OK) return s;
         if (!pl.fused.empty())
-            if (const rf_status s = join_topk_device(pl.raw0, pl.plan0, queries, corpus, pl.fused, tp.row_slot, tp.row_len, op, flags, k, sc, st, &keys, &n_batches, &n_groups, &n_units);
+            if (const rf_status s = join_topk_device(kName, JS::kF64, pl.raw0, pl.plan0, queries, corpus, pl.fused, tp.row_slot, tp.row_len, op, flags, k, sc, st, &keys, &n_batches,
+                                                     &n_groups, &n_units);
                 s != RF_OK)
                 return s;
     } else {
@@ -687,27 +730,31 @@ rf_status join_topk_call(rf_metric metric, const rf_corpus* queries, const uint6
         std::iota(rest.begin(), rest.end(), 0u);
     }
     if (sw_trace_plan())
-        std::fprintf(stderr, "[rf plan] join_topk: m=%llu k=%u batches=%u groups=%u units=%llu per_query=%zu\n", (unsigned long long)m, k, n_batches, n_groups,
+        std::fprintf(stderr, "[rf plan] %s: m=%llu k=%u batches=%u groups=%u units=%llu per_query=%zu\n", JS::kTrace, (unsigned long long)m, k, n_batches, n_groups,
                      (unsigned long long)n_units, rest.size());
-    std::vector<TopkRow> rows(rest.empty() ? 0 : (size_t)m);
+    std::vector<TopkRow<Score>> rows(rest.empty() ? 0 : (size_t)m);
     if (!rest.empty())
-        if (const rf_status s = join_topk_per_query(metric, queries, qidx, rest, corpus, op, args, flags, k, stream, &rows); s != RF_OK) return s;
+        if (const rf_status s = join_topk_per_query<Score>(metric, queries, qidx, rest, corpus, op, args, flags, k, stream, &rows); s != RF_OK) return s;
 
-    // ---- decode as rf_topk_multi_u32 does, widen, write
-    const bool desc = op == RF_OP_SIMILARITY;
+    // ---- decode as rf_topk_multi_u32 / rf_topk_multi_f64 do (the f64 rows by the very function: decode_norm_keys), widen, write
     for (size_t i = 0; i < pl.fused.size(); ++i) {
         const size_t j = pl.fused[i].pos;
         const uint64_t* best = keys.data() + i * (size_t)k;
-        uint32_t c = 0;
-        for (; c < k && best[c] != ~0ull; ++c) {
-            const uint32_t hi = (uint32_t)(best[c] >> 32);
-            out_score[j * k + c] = desc ? ~hi : hi;
-            out_index[j * k + c] = index_base + (uint32_t)best[c];
+        if constexpr (JS::kF64) {
+            out_count[j] = decode_norm_keys(best, k, metric, op, index_base, out_score + j * k, out_index + j * k);
+        } else {
+            const bool desc = op == RF_OP_SIMILARITY;
+            uint32_t c = 0;
+            for (; c < k && best[c] != ~0ull; ++c) {
+                const uint32_t hi = (uint32_t)(best[c] >> 32);
+                out_score[j * k + c] = desc ? ~hi : hi;
+                out_index[j * k + c] = index_base + (uint32_t)best[c];
+            }
+            out_count[j] = c;
         }
-        out_count[j] = c;
     }
     for (uint32_t j : rest) {
-        const TopkRow& r = rows[j];
+        const TopkRow<Score>& r = rows[j];
         for (size_t c = 0; c < r.score.size(); ++c) {
             out_score[(size_t)j * k + c] = r.score[c];
             out_index[(size_t)j * k + c] = index_base + r.index[c];
@@ -741,7 +788,15 @@ RF_ABI_CATCH
 rf_status rf_join_topk_u32(rf_metric metric, const rf_corpus* queries, const uint64_t* query_indices, uint64_t m, const rf_corpus* corpus, rf_op op, const rf_args* args_in,
                            uint32_t flags, uint32_t k, uint64_t index_base, uint32_t* out_score, uint64_t* out_index, uint32_t* out_count, void* stream)
 try {
-    return join_topk_call(metric, queries, query_indices, m, corpus, op, args_in, flags, k, index_base, out_score, out_index, out_count, stream);
+    return join_topk_call<uint32_t>(metric, queries, query_indices, m, corpus, op, args_in, flags, k, index_base, out_score, out_index, out_count, stream);
+}
+RF_ABI_CATCH
+
+// The same call by f64 score: row j is rf_topk_f64 of a comparator over row Q[j]
+rf_status rf_join_topk_f64(rf_metric metric, const rf_corpus* queries, const uint64_t* query_indices, uint64_t m, const rf_corpus* corpus, rf_op op, const rf_args* args_in,
+                           uint32_t flags, uint32_t k, uint64_t index_base, double* out_score, uint64_t* out_index, uint32_t* out_count, void* stream)
+try {
+    return join_topk_call<double>(metric, queries, query_indices, m, corpus, op, args_in, flags, k, index_base, out_score, out_index, out_count, stream);
 }
 RF_ABI_CATCH
 

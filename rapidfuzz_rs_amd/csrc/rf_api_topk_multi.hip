@@ -266,21 +266,12 @@ try {
     FusedTopk fz;
     if (const rf_status s = topk_multi_fused(true, cs, q, corpus, op, args, k, out_count, (hipStream_t)stream, &fz); s != RF_OK) return s;
     if (corpus->n == 0) return RF_OK;
-    // decode: the key's fraction is the normalized distance; which value the member returns is its plan's op (a fuzz ratio: the similarity)
+    // decode (decode_norm_keys, rf_host.hpp, shared with rf_join_topk_f64): norm_key_ratio(key) is the key's fraction a / b, the normalized distance; which value the
+    // member returns is its plan's op (a fuzz ratio: the similarity)
     uint32_t row = 0;
     for (const auto& g : fz.plan.g.groups)
-        for (uint32_t j : g) {
-            const bool as_distance = op == RF_OP_NORMALIZED_DISTANCE && cs[j]->metric != RF_FUZZ_RATIO;
-            const uint64_t* best = fz.keys.data() + (size_t)row++ * k;
-            uint32_t m = 0;
-            for (; m < k && best[m] != ~0ull; ++m) {
-                const NormRatio r = norm_key_ratio((uint32_t)(best[m] >> 32));
-                const double nd = (double)r.a / (double)r.b;
-                out_score[(size_t)j * k + m] = as_distance ? nd : 1.0 - nd;
-                out_index[(size_t)j * k + m] = index_base + (uint32_t)best[m];
-            }
-            out_count[j] = m;
-        }
+        for (uint32_t j : g)
+            out_count[j] = decode_norm_keys(fz.keys.data() + (size_t)row++ * k, k, cs[j]->metric, op, index_base, out_score + (size_t)j * k, out_index + (size_t)j * k);
 
     // ---- everything else: the single-query top-k, one call per query
     for (uint32_t j = 0; j < q; ++j) {

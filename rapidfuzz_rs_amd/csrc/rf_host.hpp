@@ -497,6 +497,23 @@ struct MultiPlan {
     void trace(const char* road, const std::string& before, const std::string& after) const;
 };
 
+// The decode of one fused row of the f64 top-k calls (rf_topk_multi_f64, rf_join_topk_f64): `best` holds k keys, norm_key(dist, maximum) << 32 | local index
+// (rf_norm_key.hpp), best first, ~0 = empty.  The key's reduced fraction a / b is the normalized distance, and (double)a / (double)b the very double emit_fin divides
+// out of dist and maximum; which value the row returns is its plan's op -- the distance only for RF_OP_NORMALIZED_DISTANCE of a metric that is not the fuzz ratio
+// (a ratio is always the similarity), 1.0 - nd otherwise.  Returns the row's count.
+inline uint32_t decode_norm_keys(const uint64_t* best, uint32_t k, rf_metric metric, rf_op op, uint64_t index_base, double* out_score, uint64_t* out_index)
+{
+    const bool as_distance = op == RF_OP_NORMALIZED_DISTANCE && metric != RF_FUZZ_RATIO;
+    uint32_t m = 0;
+    for (; m < k && best[m] != ~0ull; ++m) {
+        const NormRatio r = norm_key_ratio((uint32_t)(best[m] >> 32));
+        const double nd = (double)r.a / (double)r.b;
+        out_score[m] = as_distance ? nd : 1.0 - nd;
+        out_index[m] = index_base + (uint32_t)best[m];
+    }
+    return m;
+}
+
 // ---- shared between the translation units (definitions: the file named in the comment; they sit inside the files' extern "C" blocks)
 #pragma clang diagnostic ignored "-Wreturn-type-c-linkage"
 // (hidden: these are internal to librfgpu.so -- only the rf_* entry points of include/rfgpu.h are exported)

@@ -275,7 +275,7 @@ hipError_t launch_join_pm(const JoinPmParams& p, hipStream_t stream);
 // h_items / h_prefix: the host's copies of what jp.items / jp.prefix hold, checked (join_valid) before anything is launched
 hipError_t launch_join(RawKind raw, bool narrow, const JoinParams& jp, const JoinItem* h_items, const uint32_t* h_prefix, hipStream_t stream);
 
-// rf_join_topk.hip: the k best candidates for every row of a batch (rf_join_topk_u32) over the same work list.  A member's lists -- one per unit of its item -- fill
+// rf_join_topk.hip: the k best candidates for every row of a batch (rf_join_topk_u32 / rf_join_topk_f64) over the same work list.  A member's lists -- one per unit of its item -- fill
 // its table's segment; join_topk_select_kernel reduces a segment to the row's k keys.
 struct JoinTopkParams {
     ScanParams s;              // the scanned corpus and the finishing coefficients (plan(); an optional loose cutoff); topk_desc = similarity
@@ -288,10 +288,13 @@ struct JoinTopkParams {
     uint32_t seg_units;        // unit capacity of a segment: >= the units of every item (join_topk_seg_units)
     uint32_t seg_cap;          // seg_units * k
     uint32_t no_self;          // RF_JOIN_NO_SELF: the candidate whose local index is the member's row index is not offered
-    uint64_t* seg;             // [batch][seg_cap]: unit `ord` of table b's item leaves its merged list at b * seg_cap + ord * k + lane (score or ~score) << 32 | local index, ~0 = none
+    uint64_t* seg;             // [batch][seg_cap]: unit `ord` of table b's item leaves its merged list at b * seg_cap + ord * k + lane (score, ~score or norm_key) << 32 | local index, ~0 = none
     // join_topk_select_kernel
     const uint32_t* tab_units; // [batch] units of the item table b belongs to: the segment's first tab_units[b] * k keys are that row's
     uint64_t* keys;            // [batch][k]: the row's k best, best first, ~0 = empty
+    // (rf_join_topk_f64's comes last: the u32 kernels read every field above at the offset it always had)
+    uint32_t norm;             // 1: s is an f64 plan of a normalized op, every maximum of the launch <= kNormKeyMaxMaximum (the caller's rule, per row: norm_key_fits), and
+                               // the score image is norm_key(dist, maximum), rf_norm_key.hpp -- ascending for both ops; topk_desc is not read
 };
 // h_items / h_prefix as in launch_join; also refuses a k or a segment the kernel cannot hold
 hipError_t launch_join_topk(RawKind raw, bool narrow, const JoinTopkParams& jp, const JoinItem* h_items, const uint32_t* h_prefix, hipStream_t stream);

@@ -1,9 +1,9 @@
-// rf_join_topk.hip -- the k best candidates for every row of a packed corpus (rf_join_topk_u32; host side in rf_api_join.hip, the work list in rf_join_plan.hpp,
+// rf_join_topk.hip -- the k best candidates for every row of a packed corpus (rf_join_topk_u32 / rf_join_topk_f64; host side in rf_api_join.hip, the work list in rf_join_plan.hpp,
 // the tables by rf_join.hip join_pm_kernel).
 //   join_topk_kernel         join_kernel's unit loop and table staging around topk_multi_kernel's tile body: a workgroup walks units blockIdx.x, + gridDim.x, ...;
 //                            per unit it stages the item's (up to) 4 tables into LDS, its four wavefronts walk the unit's tiles -- 4 recurrences per lane, the next
 //                            chunk in flight across tile ends, no look and no `live` mask: there is no early-out -- and at a tile's end every member of the item
-//                            is offered one key per lane, (value or ~value) << 32 | local candidate index, into that member's register-resident WaveTopK list.
+//                            is offered one key per lane, (value, ~value or -- kNorm -- norm_key) << 32 | local candidate index, into that member's register-resident WaveTopK list.
 //                            Slots beyond it->members run on a zero table (uniform control flow) and are never offered.  TWO guards name `members`, and they are
 //                            not alike: the one around the offer is a COST guard -- a list nobody reads would only pay inserts, no result changes without it --
 //                            and the one around wavefront 0's merge and store is the CORRECTNESS guard: table0 + q of a slot beyond members is the next item's
@@ -18,6 +18,12 @@
 //                            table stage and both barriers of every one of the kJoinMembers rounds of the merge, in every unit: the rounds are not conditional on
 //                            `members`, only wavefront 0's merge and store inside them are.
 //                            No launch-wide pruning bound (topk_multi_kernel's per-query bound words): they save inserts, not columns.
+//                            kNorm (rf_join_topk_f64): the normalized ops, as topk_multi_kernel<.., kNorm = true> has them.  At a tile's end, per member, tile_fin with
+//                            the maximum made uniform, ONE norm_key_scale (the f64 division) per tile and member, fin_dist, and the key is
+//                            norm_key_scaled(dist, maximum, scale) << 32 | index (rf_norm_key.hpp) -- ascending for both ops, so topk_desc is not read; None is
+//                            emit_fin's f64 rule (norm_keep of norm_of: that division per candidate is paid under a cutoff only).  Every maximum of the launch is
+//                            within 65535: the host admits a row by norm_key_fits of ITS length and the corpus' longest candidate.  Everything else -- the no_self
+//                            compare, both guards, the barriers, the segment addressing, the selection -- is shared with the u32 instantiation.
 //   join_topk_select_kernel  one workgroup per table of the batch: topk_select over the units_of_item x k keys of the row's segment (~0 is never offered), the k
 //                            best, best first, ~0 = empty, to the row's place in the batch's key buffer.
 // LDS: 8 KiB of tables (4 KiB for the 32-bit states) + 2 KiB of lists.  Plain vector stores only; no inline assembly beyond what WaveTopK contains.
@@ -27,10 +33,11 @@
 #include "rf_internal.hpp"
 #include "rf_device.hpp"
 #include "rf_join_plan.hpp"
+#include "rf_norm_key.hpp"
 
 namespace rf {
 
-template <class State, bool kUniform>
+template <class State, bool kUniform, bool kNorm>
 __global__ __launch_bounds__(kWave* kWavesPerBlock) void join_topk_kernel(const JoinTopkParams jp)
 {
     static_assert(State::kWords == 1, "multi-query kernels are single-word");
@@ -108,8 +115,19 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void join_topk_kernel(const 
                     if ((uint32_t)q >= members) continue;  // (uniform: the item's; a cost guard, see the head comment)
                     const uint32_t raw = st[q].result(len1[q], len2);
                     bool keep;
-                    const uint32_t v = usize_value(p, raw, len2, &keep, len1[q]);  // emit_usize's arithmetic; None is not offered
-                    const uint64_t mine = ((uint64_t)(p.topk_desc ? ~v : v) << 32) | idx;
+                    uint64_t mine;
+                    if constexpr (!kNorm) {
+                        const uint32_t v = usize_value(p, raw, len2, &keep, len1[q]);  // emit_usize's arithmetic; None is not offered
+                        mine = ((uint64_t)(p.topk_desc ? ~v : v) << 32) | idx;
+                    } else {  // (topk_multi_kernel's normalized tile end: one scale per tile and member, the division of nd under a cutoff only)
+                        TileFin f = tile_fin(p, len1[q], len2);
+                        f.max = uniform(f.max);
+                        const double scale = norm_key_scale(f.max);
+                        const uint32_t dist = fin_dist(p, f, raw);
+                        keep = true;
+                        if (p.has_cutoff) keep = norm_keep(p, norm_of(dist, f.max));
+                        mine = ((uint64_t)norm_key_scaled(dist, f.max, scale) << 32) | idx;
+                    }
                     if (best[q].offer(mine, valid && keep && !(jp.no_self && idx == qidx[q]), k, lane, limit[q])) limit[q] = best[q].worst(k);
                 }
                 if (!has_next) break;  // (leaves the tile walk, never the unit loop)
@@ -148,13 +166,14 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void join_topk_select_kernel
     if (wave == 0 && lane < k) jp.keys[(size_t)b * k + lane] = best.key;
 }
 
-// raw: RAW_LEV or RAW_LCS; narrow: every query of every item <= 32 symbols.  The grid: one workgroup per unit up to scan_max_grid(), beyond it a workgroup
+// raw: RAW_LEV or RAW_LCS; narrow: every query of every item <= 32 symbols; jp.norm picks the normalized instantiation (and must agree with the plan's out_f64).  The grid: one workgroup per unit up to scan_max_grid(), beyond it a workgroup
 // walks several units.
 hipError_t launch_join_topk(RawKind raw, bool narrow, const JoinTopkParams& jp, const JoinItem* h_items, const uint32_t* h_prefix, hipStream_t stream)
 {
     const ScanParams& p = jp.s;
     if (jp.n_items == 0 || jp.n_units == 0) return hipSuccess;
-    if (!h_items || !h_prefix || !jp.items || !jp.prefix || !jp.tables || !jp.seg || p.out_f64) return hipErrorInvalidValue;
+    if (!h_items || !h_prefix || !jp.items || !jp.prefix || !jp.tables || !jp.seg || (p.out_f64 != 0) != (jp.norm != 0)) return hipErrorInvalidValue;
+    if (jp.norm && p.op != RF_OP_NORMALIZED_DISTANCE && p.op != RF_OP_NORMALIZED_SIMILARITY) return hipErrorInvalidValue;
     if (!p.data || (p.tiles && !p.orig)) return hipErrorInvalidValue;
     if (jp.k == 0 || jp.k > (uint32_t)kWave || jp.seg_units == 0 || (uint64_t)jp.seg_units * jp.k != jp.seg_cap) return hipErrorInvalidValue;
     if (!join_valid(h_items, h_prefix, jp.n_items, jp.n_units, p.n_tiles, jp.batch, narrow, jp.span)) return hipErrorInvalidValue;
@@ -163,10 +182,17 @@ hipError_t launch_join_topk(RawKind raw, bool narrow, const JoinTopkParams& jp, 
     const dim3 g(std::max(1u, std::min<uint32_t>(jp.n_units, (uint32_t)scan_max_grid()))), b(kWave * kWavesPerBlock);
     auto with_state = [&](auto state) {
         using State = typename decltype(state)::type;
+        auto with_layout = [&](auto uniform_layout) {
+            constexpr bool kU = decltype(uniform_layout)::value;
+            if (jp.norm)
+                hipLaunchKernelGGL((join_topk_kernel<State, kU, true>), g, b, 0, stream, jp);
+            else
+                hipLaunchKernelGGL((join_topk_kernel<State, kU, false>), g, b, 0, stream, jp);
+        };
         if (p.tiles)
-            hipLaunchKernelGGL((join_topk_kernel<State, false>), g, b, 0, stream, jp);
+            with_layout(std::false_type{});
         else
-            hipLaunchKernelGGL((join_topk_kernel<State, true>), g, b, 0, stream, jp);
+            with_layout(std::true_type{});
         return hipGetLastError();
     };
     if (raw == RAW_LEV) return narrow ? with_state(MultiStateTag<Lev32State>{}) : with_state(MultiStateTag<LevState<1>>{});

@@ -172,6 +172,25 @@ impl Corpus {
         })?;
         Ok((0..m).map(|j| (0..count[j] as usize).map(|t| (idx[j * kk + t], score[j * kk + t] as usize)).collect()).collect())
     }
+    /// `join_topk` by f64 score (rf_join_topk_f64): `op` is `RF_OP_NORMALIZED_DISTANCE` / `RF_OP_NORMALIZED_SIMILARITY` of the usize metrics, one of the two
+    /// similarity ops of `RF_FUZZ_RATIO`, or any op of jaro / jaro_winkler; row j holds exactly the doubles, in the (score, candidate) order, that `rf_topk_f64`
+    /// of a comparator over that row returns.  "Each record's best match by ratio": over a ragged corpus this ranking differs from `join_topk`'s.
+    #[allow(clippy::too_many_arguments)]
+    pub fn join_topk_f64(&self, queries: &Corpus, metric: std::os::raw::c_int, op: std::os::raw::c_int, args: &RfArgs, k: u32, query_indices: Option<&[u64]>, no_self: bool,
+                         index_base: u64) -> Result<Vec<Vec<(u64, f64)>>, Error> {
+        let (qi, m) = match query_indices {
+            Some(v) if v.is_empty() => return Ok(Vec::new()),
+            Some(v) => (v.as_ptr(), v.len()),
+            None => (std::ptr::null(), queries.len()),
+        };
+        let flags = if no_self { RF_JOIN_NO_SELF } else { 0 };
+        let kk = k as usize;
+        let (mut score, mut idx, mut count) = (vec![0f64; m * kk], vec![0u64; m * kk], vec![0u32; m]);
+        check(unsafe {
+            rf_join_topk_f64(metric, queries.0, qi, m as u64, self.0, op, args, flags, k, index_base, score.as_mut_ptr(), idx.as_mut_ptr(), count.as_mut_ptr(), std::ptr::null_mut())
+        })?;
+        Ok((0..m).map(|j| (0..count[j] as usize).map(|t| (idx[j * kk + t], score[j * kk + t])).collect()).collect())
+    }
     /// The same as `String`s, for a corpus of `char`s (a byte corpus reads as Latin-1: its bytes are the code points 0..255).
     pub fn take_chars(&self, indices: &[u64], index_base: u64) -> Result<Vec<String>, Error> {
         if indices.is_empty() {
