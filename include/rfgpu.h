@@ -599,20 +599,26 @@ rf_status rf_filter_multi_f64(const rf_comparator *const *cs, uint32_t q, const 
  * host while the call runs -- so a caller who cannot bound the answer counts first (capacity 0) and then passes the count; a capacity the device
  * cannot hold is RF_ERR_OOM, not a shorter answer.  A call that does not return RF_OK writes nothing.  order: RF_JOIN_BY_QUERY = ascending (position in Q,
  * candidate index), RF_JOIN_ANY = arrival order.
- * Two roads.  On the DEVICE: both corpora hold bytes, levenshtein (uniform or Indel-like weights) / indel / lcs_seq, rows of <= 64 symbols
- * whose cutoff is TIGHT (the planner's early-out rule, as rf_filter_multi_u32).  Only the rows' lengths come home; the pattern tables are
- * built out of the query corpus' payload on the device, no comparator exists and no query byte crosses PCIe.  Rows are sorted by length, cut
- * into batches (RF_JOIN_BATCH) and evaluated 4 at a time by kernels that walk a work list in device memory: per batch one table build and
- * one scan per query class that occurs (<= 32 / 33..64 symbols), however many groups of four the batch holds.  PER QUERY: every other row
- * (longer rows, osa, damerau_levenshtein, hamming / prefix / postfix, general weight tables, a loose cutoff, a `char` corpus on either side)
- * goes through rf_corpus_take, rf_comparator_new and rf_filter_u32, one row at a time -- slow by design, but no shape becomes an empty
- * answer.  RF_TRACE_PLAN prints "[rf plan] join: m=.. batches=.. groups=.. per_query=.."; RF_JOIN=0 sends every row per query.
+ * Two roads.  On the DEVICE: levenshtein (uniform or Indel-like weights) / indel / lcs_seq, rows of <= 64 symbols whose cutoff is TIGHT
+ * (the planner's early-out rule, as rf_filter_multi_u32), over corpora of either kind on either side -- bytes or `char` (rf_corpus_pack_u32):
+ * a 256-byte map built once per call takes every stored byte of the query corpus through its SYMBOL to the scanned corpus' table row, by
+ * the rule a single query is lowered with.  Only the rows' lengths come home (and, when the map has symbols it cannot place, one flag per
+ * row); the pattern tables are built out of the query corpus' payload on the device, no comparator exists and no query symbol crosses PCIe.
+ * Rows are sorted by length, cut into batches (RF_JOIN_BATCH) and evaluated 4 at a time by kernels that walk a work list in device memory:
+ * per batch one table build and one scan per query class that occurs (<= 32 / 33..64 symbols), however many groups of four the batch holds.
+ * PER QUERY: every other row -- longer rows, osa, damerau_levenshtein, hamming / prefix / postfix, general weight tables, a loose cutoff,
+ * and a row that holds a symbol the map cannot place exactly: a symbol in the OVERFLOW CLASS of either `char` corpus (more than 254
+ * distinct symbols: the rarest ones), or a symbol above 255 against a byte corpus (that row is the single-query call's
+ * RF_ERR_UNSUPPORTED, for the whole call) -- goes through rf_corpus_take[_u32], rf_comparator_new[_u32] and rf_filter_u32, one row at a
+ * time -- slow by design, but no shape becomes an empty answer.  RF_TRACE_PLAN prints
+ * "[rf plan] join: m=.. batches=.. groups=.. per_query=.."; RF_JOIN=0 sends every row per query.
  * Errors: a null queries / corpus / args / out_count, a null array with capacity != 0, an unknown order, op or flag bit, an f64-valued or
  * unknown metric, args without a cutoff: RF_ERR_INVALID_ARG, decided before either corpus is looked at or a device is touched.  m == 0 is
  * RF_OK and writes NOTHING, *out_count included, and this rule comes first: an empty `queries` with query_indices == NULL has m == 0.  Then: an index >= rf_corpus_count(queries), m != count with query_indices == NULL, m beyond 2^32 - 2, or
  * corpora on different devices: RF_ERR_INVALID_ARG, nothing written.  Either corpus empty (and m != 0): RF_OK with *out_count = 0.
  * Out of scope: f64 scores (normalized ops, fuzz ratio, jaro / jaro_winkler: rf_join_f64 below), device-resident output,
- * a multi-GPU form (shards are separate calls with their bases; their triples concatenate), and a fused road for `char` corpora. */
+ * a multi-GPU form (shards are separate calls with their bases; their triples concatenate), and a device road for rows that hold
+ * overflow-class symbols. */
 typedef enum rf_join_order { RF_JOIN_BY_QUERY = 0, RF_JOIN_ANY = 1 } rf_join_order;
 #define RF_JOIN_UPPER 1u
 rf_status rf_join_u32(rf_metric metric, const rf_corpus *queries, const uint64_t *query_indices, uint64_t m,
@@ -633,20 +639,21 @@ rf_status rf_join_u32(rf_metric metric, const rf_corpus *queries, const uint64_t
  * is all m x n pairs.
  * `capacity` is ALLOCATED as given -- 16 bytes per entry on the device here (the 8-byte pair and the double itself; at most m x n entries)
  * and 32 per entry on the host beside the caller's arrays while the call runs -- so count first (capacity 0) when the answer cannot be bounded.
- * Two roads, the u32 call's.  On the DEVICE: both corpora hold bytes, levenshtein (uniform or Indel-like weights) / indel / lcs_seq / fuzz
- * ratio, rows of <= 64 symbols whose f64 cutoff is TIGHT (the planner's early-out rule: an allowed normalized distance below 0.7 for
- * levenshtein, below 0.4 for the LCS family).  The same batches, work list and kernels with the f64 keep rule of the single-query call at
+ * Two roads, the u32 call's.  On the DEVICE: levenshtein (uniform or Indel-like weights) / indel / lcs_seq / fuzz ratio, rows of <= 64
+ * symbols whose f64 cutoff is TIGHT (the planner's early-out rule: an allowed normalized distance below 0.7 for levenshtein, below 0.4
+ * for the LCS family), over byte or `char` corpora on either side (the u32 call's symbol map).  The same batches, work list and kernels with the f64 keep rule of the single-query call at
  * a tile's end; the kernel stores the double itself, so -- unlike rf_filter_multi_f64 / rf_topk_multi_f64, which order 32-bit keys -- no
  * maximum is too large: the corpus may hold candidates of any length.  PER QUERY: every other row (jaro, jaro_winkler, osa,
- * damerau_levenshtein, hamming / prefix / postfix, general weight tables, longer rows, a loose cutoff, a `char` corpus on either side)
- * goes through rf_corpus_take, rf_comparator_new and rf_filter_f64, one row at a time.  RF_TRACE_PLAN prints
+ * damerau_levenshtein, hamming / prefix / postfix, general weight tables, longer rows, a loose cutoff, a row that holds an overflow-class
+ * symbol of either `char` corpus or a symbol above 255 against a byte corpus)
+ * goes through rf_corpus_take[_u32], rf_comparator_new[_u32] and rf_filter_f64, one row at a time.  RF_TRACE_PLAN prints
  * "[rf plan] join_f64: m=.. batches=.. groups=.. per_query=.."; RF_JOIN=0 and RF_JOIN_BATCH act as above.
  * Errors: rf_join_u32's null pointers, an unknown order, op, flag bit or metric, RF_OP_DISTANCE / RF_OP_SIMILARITY of a usize metric
  * (u32-valued: rf_join_u32), a distance op of fuzz ratio, a NaN cutoff: RF_ERR_INVALID_ARG, decided before either corpus is looked at or a
  * device is touched, nothing written.  Then, as above: an index out of range, m != count with query_indices == NULL, m beyond 2^32 - 2,
  * corpora on different devices: RF_ERR_INVALID_ARG; either corpus empty (and m != 0): RF_OK with *out_count = 0.
  * Out of scope: a host-built integer limit per (query length, tile length) in place of the f64 division of every look, device-resident
- * output, a multi-GPU form, and a fused road for `char` corpora. */
+ * output, a multi-GPU form, and a device road for rows that hold overflow-class symbols. */
 rf_status rf_join_f64(rf_metric metric, const rf_corpus *queries, const uint64_t *query_indices, uint64_t m,
                       const rf_corpus *corpus, rf_op op, const rf_args *args, uint32_t flags,
                       uint64_t query_base, uint64_t index_base, uint64_t capacity,
@@ -667,8 +674,9 @@ rf_status rf_join_f64(rf_metric metric, const rf_corpus *queries, const uint64_t
  * offered; both indices are taken before index_base is added (as RF_JOIN_UPPER compares).  A self-join then returns each record's k nearest
  * OTHER records.  RF_JOIN_UPPER and every other bit are RF_ERR_INVALID_ARG here; rf_join_u32 / rf_join_f64 go on refusing every bit but
  * RF_JOIN_UPPER.
- * Two roads (as rf_join_u32).  On the DEVICE: both corpora hold bytes, levenshtein (uniform or Indel-like weights) / indel / lcs_seq, rows
- * of <= 64 symbols, k <= 64, and a plan rf_topk_multi_u32 would fuse -- no early-out, i.e. no cutoff or a loose one.  Only the rows' lengths
+ * Two roads (as rf_join_u32).  On the DEVICE: levenshtein (uniform or Indel-like weights) / indel / lcs_seq, rows of <= 64 symbols, k <= 64,
+ * and a plan rf_topk_multi_u32 would fuse -- no early-out, i.e. no cutoff or a loose one -- over byte or `char` corpora on either side
+ * (rf_join_u32's symbol map).  Only the rows' lengths
  * come home; tables are built on the device out of the query corpus' payload; rows are sorted by length, cut into batches (RF_JOIN_BATCH)
  * and evaluated 4 at a time by a kernel that walks a work list and keeps four register-resident k-entry lists per lane; per batch one table
  * build, one scan per query class that occurs and one selection launch.  The call allocates on the device, per row of a batch, 2 KiB of
@@ -676,8 +684,9 @@ rf_status rf_join_f64(rf_metric metric, const rf_corpus *queries, const uint64_t
  * runs, so a full batch of 16384 rows at k = 64 stays within ~25 MiB of segments -- and k x 8 bytes of keys per fused row of the CALL, which
  * come home ONCE, after the last batch (chosen over a copy per batch: at 65536 rows x k = 64 that is 32 MiB on either side, and a copy per
  * batch would synchronize the stream per batch); the host holds the same k x 8 bytes per row while the call runs.  PER QUERY: every other
- * row (longer rows, k > 64, a tight cutoff, osa, damerau_levenshtein, hamming / prefix / postfix, general weight tables, a `char` corpus on
- * either side) goes through rf_corpus_take, rf_comparator_new and rf_topk_u32, one row at a time; under RF_JOIN_NO_SELF that road asks for
+ * row (longer rows, k > 64, a tight cutoff, osa, damerau_levenshtein, hamming / prefix / postfix, general weight tables, a row that holds
+ * an overflow-class symbol of either `char` corpus or a symbol above 255 against a byte corpus) goes through rf_corpus_take[_u32],
+ * rf_comparator_new[_u32] and rf_topk_u32, one row at a time; under RF_JOIN_NO_SELF that road asks for
  * k + 1 entries and drops the row's own, or the last one if its own is not among them.  RF_TRACE_PLAN prints
  * "[rf plan] join_topk: m=.. k=.. batches=.. groups=.. units=.. per_query=.."; RF_JOIN=0 sends every row per query, RF_JOIN_BATCH bounds a
  * batch, RF_JOIN_TOPK_UNITS forces the units of a batch (results are identical for every value).
@@ -689,7 +698,8 @@ rf_status rf_join_f64(rf_metric metric, const rf_corpus *queries, const uint64_t
  * A call that does not return RF_OK writes nothing.
  * (By f64 score -- normalized_*, fuzz ratio, jaro / jaro_winkler: rf_join_topk_f64 below.)
  * Out of scope: an early-out variant for tight cutoffs, device-resident output, a multi-GPU form (shards
- * are separate calls with their bases; their rows merge on the host with rf_topk_merge_u32), and a fused road for `char` corpora. */
+ * are separate calls with their bases; their rows merge on the host with rf_topk_merge_u32), and a device road for rows that hold
+ * overflow-class symbols. */
 #define RF_JOIN_NO_SELF 2u
 rf_status rf_join_topk_u32(rf_metric metric, const rf_corpus *queries, const uint64_t *query_indices, uint64_t m,
                            const rf_corpus *corpus, rf_op op, const rf_args *args, uint32_t flags, uint32_t k,
@@ -708,7 +718,7 @@ rf_status rf_join_topk_u32(rf_metric metric, const rf_corpus *queries, const uin
  * args->cutoff_f64 (NaN = no cutoff).  Accepted (metric, op) pairs are rf_join_f64's and rf_topk_multi_f64's: RF_OP_NORMALIZED_DISTANCE /
  * RF_OP_NORMALIZED_SIMILARITY of the usize metrics, RF_FUZZ_RATIO with its two similarity ops (with and without
  * RF_FLAG_RATIO_INDEL_NORMALIZATION), every op of RF_JARO / RF_JARO_WINKLER.
- * Two roads, the u32 call's.  On the DEVICE: both corpora hold bytes, levenshtein (uniform or Indel-like weights) / indel / lcs_seq / fuzz
+ * Two roads, the u32 call's.  On the DEVICE: byte or `char` corpora on either side, levenshtein (uniform or Indel-like weights) / indel / lcs_seq / fuzz
  * ratio, rows of <= 64 symbols, k <= 64, a plan rf_topk_multi_f64 would fuse -- no early-out, i.e. no cutoff or a loose one -- and every
  * maximum of the row's scan within 65535: the in-scan lists order by the 32-bit image norm_key(dist, maximum) of the normalized distance
  * (exact and order-preserving up to there; both ops rank by ascending key, equal ratios of different fractions -- 2/4 and 4/8 -- get one
@@ -719,7 +729,8 @@ rf_status rf_join_topk_u32(rf_metric metric, const rf_corpus *queries, const uin
  * (double)a / (double)b is the double the single-query kernels divide out of dist and maximum, returned as it is for
  * RF_OP_NORMALIZED_DISTANCE of a metric that is not fuzz ratio and as 1.0 - that otherwise.  PER QUERY: every other row (jaro,
  * jaro_winkler, osa, damerau_levenshtein, hamming / prefix / postfix, general weight tables, rows beyond 64 symbols, k > 64, a tight cutoff, a
- * maximum beyond 65535, a `char` corpus on either side) goes through rf_corpus_take, rf_comparator_new and rf_topk_f64, one row at a time;
+ * maximum beyond 65535, a row that holds an overflow-class symbol of either `char` corpus or a symbol above 255 against a byte corpus) goes
+ * through rf_corpus_take[_u32], rf_comparator_new[_u32] and rf_topk_f64, one row at a time;
  * under RF_JOIN_NO_SELF that road asks for k + 1 entries and drops the row's own, or the last one if its own is not among them.  Slow by
  * design, but no shape becomes an empty answer.  RF_TRACE_PLAN prints
  * "[rf plan] join_topk_f64: m=.. k=.. batches=.. groups=.. units=.. per_query=.."; RF_JOIN=0, RF_JOIN_BATCH and RF_JOIN_TOPK_UNITS act as
@@ -730,7 +741,8 @@ rf_status rf_join_topk_u32(rf_metric metric, const rf_corpus *queries, const uin
  * with query_indices == NULL, m beyond 2^32 - 2, corpora on different devices: RF_ERR_INVALID_ARG; either corpus empty: RF_OK with every
  * count 0.
  * Out of scope: a wider key for maxima beyond 65535, an early-out variant for tight cutoffs, device-resident output, a multi-GPU form
- * (shards are separate calls with their bases; their rows merge on the host), and a fused road for `char` corpora. */
+ * (shards are separate calls with their bases; their rows merge on the host), and a fused road for `char` corpora rows that hold
+ * overflow-class symbols (every other row of a `char` corpus fuses). */
 rf_status rf_join_topk_f64(rf_metric metric, const rf_corpus *queries, const uint64_t *query_indices, uint64_t m,
                            const rf_corpus *corpus, rf_op op, const rf_args *args, uint32_t flags, uint32_t k,
                            uint64_t index_base,

@@ -3,11 +3,17 @@
 // JoinScore<Score> -- the entry point's name and trace prefix, whether plan() is asked for f64, which rf_filter_* the per-query road calls, which score buffer the
 // kernel fills -- and the `f64` arm of check_join_args: the accepted (metric, op) pairs and where the cutoff sits.
 // Two roads:
-//   device      both corpora hold bytes, the metric and weights plan to a fused recurrence (fusable_base), the row has <= 64 symbols and its plan is `early`:
-//               the rows' lengths come home (4 bytes per row, never a symbol), plan() runs once per distinct length -- a byte query reaches its plan through its
+//   device      the metric and weights plan to a fused recurrence (fusable_base), the row has <= 64 symbols, every one of them can be placed exactly in the
+//               scanned corpus' table, and its plan is `early`.  Either corpus may hold bytes or `char`s: the call's row map (rf_join_xlat.hpp, 256 bytes built
+//               on the host) takes a stored byte of the query corpus through its SYMBOL to the scanned corpus' table row.  A row that holds an overflow-class
+//               symbol of either corpus, or a symbol above 0xFF against a byte corpus, cannot be placed: when the map has such values join_bad_kernel flags
+//               those rows on the device and the flags come home with the lengths.
+//               The rows' lengths come home (4 bytes per row, never a symbol), plan() runs once per distinct length -- a byte query reaches its plan through its
 //               length alone -- the fusable rows are sorted by length and cut into batches; per batch one join_pm_kernel builds the tables out of the query
 //               corpus' payload and one join_kernel per class (narrow / wide) that occurs walks the batch's work list (rf_join_plan.hpp, rf_join.hip).  One
 //               64-bit counter and one triple buffer serve the whole call; they come home once, after the last batch.
+//               Candidates that hold overflow-class symbols store the overflow id, whose row no fused query has a bit in: they match nothing there, which is
+//               exact because every query row with such a symbol went per query.
 //               rf_join_f64 plans with f64_out (a fuzz ratio becomes the normalized similarity of its inner metric in plan()) and the kernel stores the double
 //               itself: no 32-bit key is ordered, so no maximum of the corpus is too large.
 //   per query   every other row: rf_corpus_take[_u32] of the row, rf_comparator_new[_u32], rf_filter_u32 / rf_filter_f64, append.  Plain host code, slow by design, total.
@@ -27,8 +33,12 @@
 
 #include "rf_host.hpp"
 
+#include "rf_alphabet.hpp"
 #include "rf_join_plan.hpp"
+#include "rf_join_xlat.hpp"
 #include "rf_take_addr.hpp"
+
+static_assert(rf::kXlatOverflowId == kOverflowId && rf::kXlatAbsentId == kAbsentId && rf::kXlatNoSymbol == rf::kReservedSymbol, "rf_join_xlat.hpp restates the ids of a `char` corpus");
 
 // (all three calls read the two switches through these)
 // A/B switch: 0 sends every row down the per-query road (identical results)
@@ -80,13 +90,12 @@ struct ComparatorOwner : NoCopy {
 struct JoinBatches : NoCopy {
     uint32_t B = 0;         // most rows of a batch
     size_t max_batch = 0;   // ... of this call's
-    uint8_t* d_ctl = nullptr;  // 512 bytes: [256 for the road's own counters, zeroed | inverse sigma of the query corpus]
+    uint8_t* d_ctl = nullptr;  // 512 bytes: [256 for the road's own counters, zeroed | the call's row map: query corpus' stored symbol -> scanned corpus' table row]
     uint64_t* d_tables = nullptr;
     uint32_t* d_blob = nullptr;
     size_t blob_words = 0;
     std::deque<std::vector<uint32_t>> blobs;  // the host side of every upload stays alive until the stream has drained
     JoinPmParams pm{};
-    uint8_t inv[256];       // (the upload's host side)
     JoinList lists[2];      // narrow, wide: the batch run() saw last
     size_t items_at[2] = {0, 0}, prefix_at[2] = {0, 0}, tail_at = 0;
     bool outgrew = false;
@@ -100,16 +109,15 @@ struct JoinBatches : NoCopy {
     const uint32_t* prefix(int k) const { return d_blob + prefix_at[k]; }
     const uint32_t* tail() const { return d_blob + tail_at; }
 
-    // tail_words_per_row: words the caller appends per row of a batch
-    rf_status init(const rf_corpus* queries, const rf_corpus* corpus, size_t n_fused, const uint32_t* d_row_slot, const uint32_t* d_row_len, size_t tail_words_per_row, ScratchSet& sc,
+    // tail_words_per_row: words the caller appends per row of a batch; xl: the call's row map, alive until the stream has drained
+    rf_status init(const rf_corpus* queries, const JoinXlat& xl, size_t n_fused, const uint32_t* d_row_slot, const uint32_t* d_row_len, size_t tail_words_per_row, ScratchSet& sc,
                    hipStream_t st)
     {
         B = sw_join_batch();
         max_batch = std::min<size_t>(B, n_fused);
         RF_HIP(sc.get(&d_ctl, 512));
-        take_inverse_sigma(queries->sigma, inv);
         RF_HIP(hipMemsetAsync(d_ctl, 0, 256, st));
-        RF_HIP(hipMemcpyAsync(d_ctl + 256, inv, 256, hipMemcpyHostToDevice, st));
+        RF_HIP(hipMemcpyAsync(d_ctl + 256, xl.row_of, 256, hipMemcpyHostToDevice, st));
         RF_HIP(sc.get(&d_tables, max_batch * 256 * sizeof(uint64_t)));
         // at most max_batch items and max_batch + 2 prefix entries
         blob_words = max_batch + max_batch * (sizeof(JoinItem) / 4) + max_batch + 2 + max_batch * tail_words_per_row;
@@ -120,8 +128,7 @@ struct JoinBatches : NoCopy {
         pm.s.uniform_tile_bytes = (uint32_t)tile_bytes(queries->uniform_len);
         pm.n_slots = queries->uniform ? queries->n_tiles * (uint32_t)kWave : (uint32_t)queries->n_slots;
         pm.row_slot = d_row_slot, pm.row_len = d_row_len;
-        pm.inv_sigma = d_ctl + 256;
-        pm.sigma = corpus->d_sigma;
+        pm.row_of = d_ctl + 256;
         pm.tables = d_tables;
         return RF_OK;
     }
@@ -166,13 +173,13 @@ inline rf_status join_hip_status(const char* name, const char* where, hipError_t
 
 // the device road over the rows `fused` (sorted): triples of the first `cap` pairs to arrive into `out`, the true number of pairs into *total
 template <class Score>
-rf_status join_device(RawKind raw, const ScanParams& plan0, const rf_corpus* queries, const rf_corpus* corpus, const std::vector<JoinQuery>& fused, const uint32_t* d_row_slot,
+rf_status join_device(RawKind raw, const ScanParams& plan0, const rf_corpus* queries, const rf_corpus* corpus, const JoinXlat& xl, const std::vector<JoinQuery>& fused, const uint32_t* d_row_slot,
                       const uint32_t* d_row_len, uint32_t flags, uint64_t cap, ScratchSet& sc, hipStream_t st, std::vector<Triple<Score>>* out, uint64_t* total, uint32_t* n_batches,
                       uint32_t* n_groups)
 {
-    // per-call device state: [counter | inverse sigma of the query corpus], the triple buffer, and per-batch scratch bounded by the batch
+    // per-call device state: [counter | row map], the triple buffer, and per-batch scratch bounded by the batch
     JoinBatches jb;
-    if (const rf_status s = jb.init(queries, corpus, fused.size(), d_row_slot, d_row_len, 0, sc, st); s != RF_OK) return s;
+    if (const rf_status s = jb.init(queries, xl, fused.size(), d_row_slot, d_row_len, 0, sc, st); s != RF_OK) return s;
     unsigned long long* d_count = reinterpret_cast<unsigned long long*>(jb.d_ctl);
     uint64_t* d_pairs = nullptr;
     Score* d_scores = nullptr;
@@ -367,8 +374,27 @@ rf_status join_rows(const char* fn, const rf_corpus* queries, const rf_corpus* c
     return RF_OK;
 }
 
-// the rows' slots and lengths (take_rows_len_kernel) into tp->row_slot / tp->row_len; the lengths come home
-rf_status join_lengths(const char* fn, const rf_corpus* queries, const std::vector<uint32_t>& qidx, ScratchSet& sc, hipStream_t st, TakeParams* tp_out, std::vector<uint32_t>* lens)
+// The call's row map (rf_join_xlat.hpp) out of the two handles.  false: the scanned corpus' sigma gives the absent id a row in use -- no packer makes such a
+// corpus -- and nothing may be fused
+bool join_xlat_of(const rf_corpus* queries, const rf_corpus* corpus, JoinXlat* xl)
+{
+    uint32_t sym_q[256], sym_c[256];
+    auto view = [](const rf_corpus* c, uint32_t* sym) {
+        for (uint32_t id = 0; id < 256; ++id) sym[id] = kXlatNoSymbol;
+        for (const auto& kv : c->alphabet) sym[kv.second] = kv.first;
+        return JoinXlatCorpus{c->wide, c->sigma, sym, !c->overflow.empty()};
+    };
+    return join_xlat_build(view(queries, sym_q), view(corpus, sym_c), [&](uint32_t sym) -> uint32_t {
+        const auto a = corpus->alphabet.find(sym);
+        if (a != corpus->alphabet.end()) return a->second;
+        return corpus->overflow.count(sym) ? kXlatOverflowId : kXlatAbsentId;
+    }, xl);
+}
+
+// the rows' slots and lengths (take_rows_len_kernel) into tp->row_slot / tp->row_len; the lengths come home -- and with them, in the same synchronization, one
+// flag per row when the row map has values it cannot place (xl.any_bad; join_bad_kernel): `flagged` stays empty otherwise
+rf_status join_lengths(const char* fn, const rf_corpus* queries, const JoinXlat& xl, const std::vector<uint32_t>& qidx, ScratchSet& sc, hipStream_t st, TakeParams* tp_out,
+                       std::vector<uint32_t>* lens, std::vector<uint32_t>* flagged)
 {
     const size_t m = qidx.size();
     TakeParams& tp = *tp_out;
@@ -381,25 +407,42 @@ rf_status join_lengths(const char* fn, const rf_corpus* queries, const std::vect
     uint32_t* d_idx = nullptr;
     RF_HIP(sc.get(&d_idx, m * sizeof(uint32_t)));
     RF_HIP(sc.get(&tp.row_slot, m * sizeof(uint32_t)));
-    RF_HIP(sc.get(&tp.row_len, m * sizeof(uint32_t)));
+    const size_t words = xl.any_bad ? 2 * m : m;  // [lengths | flags]
+    RF_HIP(sc.get(&tp.row_len, words * sizeof(uint32_t)));
+    uint8_t* d_bad = nullptr;
+    if (xl.any_bad) RF_HIP(sc.get(&d_bad, 256));
     if (!queries->uniform)
         if (const rf_status s = corpus_take_slot_of(queries, st, &tp.slot_of); s != RF_OK) return s;
-    lens->resize(m);
+    lens->resize(words);
     hipError_t e = hipMemcpyAsync(d_idx, qidx.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice, st);
     tp.idx = d_idx, tp.m = m;
     if (e == hipSuccess) e = launch_take_rows_len(tp, st);
-    if (e == hipSuccess) e = copy_home(lens->data(), tp.row_len, m * sizeof(uint32_t), st);
+    if (e == hipSuccess && xl.any_bad) {
+        e = hipMemcpyAsync(d_bad, xl.bad, 256, hipMemcpyHostToDevice, st);  // (xl outlives the call's last synchronization)
+        JoinBadParams bp{};
+        bp.s = tp.s, bp.n_slots = tp.n_slots;
+        bp.row_slot = tp.row_slot, bp.row_len = tp.row_len;
+        bp.bad = d_bad, bp.flags = tp.row_len + m, bp.m = m;
+        if (e == hipSuccess) e = launch_join_bad(bp, st);
+    }
+    if (e == hipSuccess) e = copy_home(lens->data(), tp.row_len, words * sizeof(uint32_t), st);
     else (void)hipStreamSynchronize(st);
     if (e != hipSuccess) {
         (void)hipGetLastError();
         set_error(std::string(fn) + ", query lengths: " + hipGetErrorString(e));
         return e == hipErrorOutOfMemory ? RF_ERR_OOM : RF_ERR_HIP;
     }
+    flagged->assign(lens->begin() + m, lens->end());
+    lens->resize(m);
     return RF_OK;
 }
 
-// One plan per distinct length: plan() reads of a byte comparator its metric and its length (the query's head and bytes only for kernels no fused road runs).
-// A row whose plan fusable(p, raw) accepts goes to `fused` with the plan's tile window, every other row to `rest`; plan0 / raw0 are the first accepted plan's.
+// One plan per distinct length: plan() reads of a byte comparator its metric and its length (the query's head and bytes only for kernels no fused road runs),
+// and of the corpus nothing that depends on its kind -- a `char` corpus is searched through a lowered BYTE comparator of the same length (resolve()), which is
+// what the probe stands for.  What does look at symbols (the 6-bit image, the head plane) is decided in run_many, which no fused road passes; the band needs a
+// query of two words or more.
+// A row whose plan fusable(p, raw) accepts goes to `fused` with the plan's tile window, every other row to `rest` -- and so does every row `flagged` (empty: none
+// is) names: it holds a symbol the row map cannot place; plan0 / raw0 are the first accepted plan's.
 struct JoinPlanned {
     std::vector<JoinQuery> fused;
     ScanParams plan0{};
@@ -407,7 +450,7 @@ struct JoinPlanned {
 };
 template <class Fusable>
 rf_status join_plan_rows(rf_metric metric, const rf_corpus* corpus, rf_op op, const rf_args* args, bool f64, const std::vector<uint32_t>& qidx, const std::vector<uint32_t>& lens,
-                         Fusable&& fusable, JoinPlanned* out, std::vector<uint32_t>* rest)
+                         const std::vector<uint32_t>& flagged, Fusable&& fusable, JoinPlanned* out, std::vector<uint32_t>* rest)
 {
     struct LenPlan {
         bool planned = false, fusable = false;
@@ -417,7 +460,7 @@ rf_status join_plan_rows(rf_metric metric, const rf_corpus* corpus, rf_op op, co
     bool have_plan0 = false;
     for (size_t j = 0; j < qidx.size(); ++j) {
         const uint32_t len = lens[j];
-        if (len > kJoinMaxLen) {
+        if (len > kJoinMaxLen || (!flagged.empty() && flagged[j])) {
             rest->push_back((uint32_t)j);
             continue;
         }
@@ -478,7 +521,8 @@ rf_status join_call(rf_metric metric, const rf_corpus* queries, const uint64_t* 
     std::vector<uint32_t> rest;  // positions of Q for the per-query road
     uint32_t n_batches = 0, n_groups = 0;
     const bool device_metric = metric == RF_LEVENSHTEIN || metric == RF_INDEL || metric == RF_LCS_SEQ || (JS::kF64 && metric == RF_FUZZ_RATIO);
-    if (sw_join() && device_metric && !queries->wide && !corpus->wide) {
+    JoinXlat xl;  // (lives to the end of the call: uploads read it)
+    if (sw_join() && device_metric && join_xlat_of(queries, corpus, &xl)) {
         DeviceGuard guard(corpus->device);
         if (!guard.ok) {
             set_error("cannot select the corpus' device");
@@ -486,15 +530,15 @@ rf_status join_call(rf_metric metric, const rf_corpus* queries, const uint64_t* 
         }
         ScratchSet sc(st);
         TakeParams tp;
-        std::vector<uint32_t> lens;
-        if (const rf_status s = join_lengths(JS::kName, queries, qidx, sc, st, &tp, &lens); s != RF_OK) return s;
+        std::vector<uint32_t> lens, flagged;
+        if (const rf_status s = join_lengths(JS::kName, queries, xl, qidx, sc, st, &tp, &lens, &flagged); s != RF_OK) return s;
         JoinPlanned pl;
         // (a tight cutoff: the planner's early-out rule)
-        if (const rf_status s = join_plan_rows(metric, corpus, op, args, JS::kF64, qidx, lens, [](const ScanParams& p, RawKind) { return p.early && p.has_cutoff; }, &pl, &rest); s != RF_OK)
+        if (const rf_status s = join_plan_rows(metric, corpus, op, args, JS::kF64, qidx, lens, flagged, [](const ScanParams& p, RawKind) { return p.early && p.has_cutoff; }, &pl, &rest); s != RF_OK)
             return s;
         if (!pl.fused.empty()) {
             const uint64_t cap = std::min<uint64_t>(capacity, (uint64_t)pl.fused.size() * corpus->n);
-            if (const rf_status s = join_device(pl.raw0, pl.plan0, queries, corpus, pl.fused, tp.row_slot, tp.row_len, flags, cap, sc, st, &triples, &total, &n_batches, &n_groups); s != RF_OK)
+            if (const rf_status s = join_device(pl.raw0, pl.plan0, queries, corpus, xl, pl.fused, tp.row_slot, tp.row_len, flags, cap, sc, st, &triples, &total, &n_batches, &n_groups); s != RF_OK)
                 return s;
         }
     } else {
@@ -551,12 +595,12 @@ struct JoinTopkScore<double> {
 // items (join_topk_span), the work lists, the tables, the batch's segments filled with ~0, one join_topk_kernel per class that occurs, one selection launch into the
 // batch's rows of the call's key buffer.  The keys come home once, after the last batch.  `norm` (rf_join_topk_f64): plan0 is an f64 plan of a normalized op and the keys
 // are norm_key images (the kernel's kNorm instantiation).
-rf_status join_topk_device(const char* kName, bool norm, RawKind raw, const ScanParams& plan0, const rf_corpus* queries, const rf_corpus* corpus, const std::vector<JoinQuery>& fused,
+rf_status join_topk_device(const char* kName, bool norm, RawKind raw, const ScanParams& plan0, const rf_corpus* queries, const rf_corpus* corpus, const JoinXlat& xl, const std::vector<JoinQuery>& fused,
                            const uint32_t* d_row_slot, const uint32_t* d_row_len, rf_op op, uint32_t flags, uint32_t k, ScratchSet& sc, hipStream_t st, std::vector<uint64_t>* keys,
                            uint32_t* n_batches, uint32_t* n_groups, uint64_t* n_units)
 {
     JoinBatches jb;
-    if (const rf_status s = jb.init(queries, corpus, fused.size(), d_row_slot, d_row_len, 1, sc, st); s != RF_OK) return s;
+    if (const rf_status s = jb.init(queries, xl, fused.size(), d_row_slot, d_row_len, 1, sc, st); s != RF_OK) return s;
     const uint32_t n_tiles = corpus->n_tiles;
     const uint32_t forced = sw_join_topk_units();
     const uint32_t target = forced ? forced : (uint32_t)std::max(1, scan_max_grid());
@@ -693,7 +737,8 @@ rf_status join_topk_call(rf_metric metric, const rf_corpus* queries, const uint6
     uint32_t n_batches = 0, n_groups = 0;
     uint64_t n_units = 0;
     const bool device_metric = metric == RF_LEVENSHTEIN || metric == RF_INDEL || metric == RF_LCS_SEQ || (JS::kF64 && metric == RF_FUZZ_RATIO);
-    if (sw_join() && device_metric && !queries->wide && !corpus->wide && k <= (uint32_t)kWave) {
+    JoinXlat xl;  // (lives to the end of the call: uploads read it)
+    if (sw_join() && device_metric && k <= (uint32_t)kWave && join_xlat_of(queries, corpus, &xl)) {
         DeviceGuard guard(corpus->device);
         if (!guard.ok) {
             set_error("cannot select the corpus' device");
@@ -701,8 +746,8 @@ rf_status join_topk_call(rf_metric metric, const rf_corpus* queries, const uint6
         }
         ScratchSet sc(st);
         TakeParams tp;
-        std::vector<uint32_t> lens;
-        if (const rf_status s = join_lengths(kName, queries, qidx, sc, st, &tp, &lens); s != RF_OK) return s;
+        std::vector<uint32_t> lens, flagged;
+        if (const rf_status s = join_lengths(kName, queries, xl, qidx, sc, st, &tp, &lens, &flagged); s != RF_OK) return s;
         // (what rf_topk_multi_u32 / rf_topk_multi_f64 fuse: no early-out -- no cutoff or a loose one -- and one kernel family, finishing and factor for the whole
         // launch; by f64 score also norm_key_fits, PER ROW: the maximum grows with the row's length, so over one corpus shorter rows may fuse while longer ones go
         // per query)
@@ -719,9 +764,9 @@ rf_status join_topk_call(rf_metric metric, const rf_corpus* queries, const uint6
             if (!have_first) first = key, have_first = true;
             return key == first;
         };
-        if (const rf_status s = join_plan_rows(metric, corpus, op, args, JS::kF64, qidx, lens, fusable, &pl, &rest); s != RF_OK) return s;
+        if (const rf_status s = join_plan_rows(metric, corpus, op, args, JS::kF64, qidx, lens, flagged, fusable, &pl, &rest); s != RF_OK) return s;
         if (!pl.fused.empty())
-            if (const rf_status s = join_topk_device(kName, JS::kF64, pl.raw0, pl.plan0, queries, corpus, pl.fused, tp.row_slot, tp.row_len, op, flags, k, sc, st, &keys, &n_batches,
+            if (const rf_status s = join_topk_device(kName, JS::kF64, pl.raw0, pl.plan0, queries, corpus, xl, pl.fused, tp.row_slot, tp.row_len, op, flags, k, sc, st, &keys, &n_batches,
                                                      &n_groups, &n_units);
                 s != RF_OK)
                 return s;

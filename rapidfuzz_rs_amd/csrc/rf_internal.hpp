@@ -251,9 +251,18 @@ struct JoinPmParams {
     const uint32_t* row_len;   // [m] ... and its length
     const uint32_t* rows;      // [batch] table b is built for row rows[b] of Q
     uint32_t batch;
-    const uint8_t* inv_sigma;  // 256 bytes: the query corpus' stored symbol -> the original byte
-    const uint8_t* sigma;      // 256 bytes: original byte -> the symbol the SCANNED corpus stores
-    uint64_t* tables;          // [batch][256]: bit i of row sigma[c] <=> symbol i of the query is c -- the rows the scan's LDS tables have
+    const uint8_t* row_of;     // 256 bytes: the query corpus' stored symbol -> the row of the SCANNED corpus' table its symbol owns (rf_join_xlat.hpp)
+    uint64_t* tables;          // [batch][256]: bit i of row row_of[s] <=> symbol i of the query is stored as s -- the rows the scan's LDS tables have
+};
+// ... and which rows of Q hold a stored symbol the row map cannot place (rf_join_xlat.hpp `bad`): those go down the per-query road
+struct JoinBadParams {
+    ScanParams s;              // the QUERY corpus, as in JoinPmParams
+    uint32_t n_slots;
+    const uint32_t* row_slot;  // [m]
+    const uint32_t* row_len;   // [m]
+    const uint8_t* bad;        // 256 bytes: stored symbol -> 1 when its symbol cannot be placed exactly
+    uint32_t* flags;           // [m] 1: the row has at most kJoinMaxLen symbols and one of them is bad; else 0
+    uint64_t m;
 };
 struct JoinParams {
     ScanParams s;              // the scanned corpus, the finishing coefficients and the cutoff (plan()); len1 / tile_begin / tile_end are the items'
@@ -272,6 +281,7 @@ struct JoinParams {
     double* scores_f64;        // [cap] the double emit_fin would have written, in place of `scores`
 };
 hipError_t launch_join_pm(const JoinPmParams& p, hipStream_t stream);
+hipError_t launch_join_bad(const JoinBadParams& p, hipStream_t stream);
 // h_items / h_prefix: the host's copies of what jp.items / jp.prefix hold, checked (join_valid) before anything is launched
 hipError_t launch_join(RawKind raw, bool narrow, const JoinParams& jp, const JoinItem* h_items, const uint32_t* h_prefix, hipStream_t stream);
 

@@ -1,8 +1,13 @@
 // rf_join.hip -- all pairs of two packed corpora within a tight cutoff (rf_join_u32 / rf_join_f64; host side in rf_api_join.hip, the work list in rf_join_plan.hpp).
-//   join_pm_kernel   a batch of B queries straight out of the QUERY corpus' packed payload (rf_take_addr.hpp's addresses, un-renamed through that corpus'
-//                    inverse sigma as rf_take.hip does) into B single-word pattern tables of 256 x u64, written AT THE SCANNED CORPUS' SIGMA ROWS: row sigma[c]
-//                    of table b has bit i set when symbol i of query b is c.  That is the form the scans keep in LDS, so join_kernel stages a table with a
-//                    straight coalesced 2 KiB copy.  A symbol the scanned corpus never stores owns a row no candidate byte names: it matches nothing.
+//   join_pm_kernel   a batch of B queries straight out of the QUERY corpus' packed payload (rf_take_addr.hpp's addresses) into B single-word pattern tables of
+//                    256 x u64, written AT THE SCANNED CORPUS' SIGMA ROWS: row row_of[s] of table b has bit i set when symbol i of query b is stored as s.
+//                    row_of (rf_join_xlat.hpp, built on the host once per call) goes through the SYMBOLS -- un-rename by the query corpus' inverse sigma, id ->
+//                    symbol for a `char` corpus, the symbol's id in the scanned corpus, that corpus' sigma -- so one kernel serves every pair of corpus kinds.
+//                    The tables are the form the scans keep in LDS, so join_kernel stages one with a straight coalesced 2 KiB copy.  A symbol the scanned
+//                    corpus never stores owns a row no candidate byte names: it matches nothing.
+//   join_bad_kernel  launched only when the row map has a stored value it cannot place (an overflow-class symbol of either corpus, a symbol above 0xFF against
+//                    a byte corpus): a wavefront per row of Q, one payload byte per lane, a lookup in the 256-byte `bad` table, a ballot, one flag per row.
+//                    Flagged rows never reach join_pm_kernel: they go down the per-query road.
 //   join_kernel      filter_multi_kernel's tile body -- 4 recurrences per lane, the look after column 8 of a full first chunk and at every chunk's end, the
 //                    `live` mask, the next tile's first chunk prefetched -- over a WORK LIST in device memory instead of one launch per group of queries.  A
 //                    workgroup walks units blockIdx.x, + gridDim.x, ...: per unit it stages the item's (up to) 4 tables into LDS and its four wavefronts walk
@@ -47,7 +52,7 @@ __global__ __launch_bounds__(kJoinPmThreads) void join_pm_kernel(const JoinPmPar
         else
             base = take_uniform_base(t, p.s.uniform_len);
         const uint32_t stored = p.s.data[take_byte_at(base, take_lane_of(slot), i)];
-        const uint32_t row = p.sigma[p.inv_sigma[stored]];
+        const uint32_t row = p.row_of[stored];
         atomicOr(&tab[row], 1ull << i);
     }
     __syncthreads();
@@ -57,8 +62,40 @@ __global__ __launch_bounds__(kJoinPmThreads) void join_pm_kernel(const JoinPmPar
 hipError_t launch_join_pm(const JoinPmParams& p, hipStream_t stream)
 {
     if (p.batch == 0) return hipSuccess;
-    if (!p.rows || !p.row_slot || !p.row_len || !p.tables || !p.inv_sigma || !p.sigma || !p.s.data) return hipErrorInvalidValue;
+    if (!p.rows || !p.row_slot || !p.row_len || !p.tables || !p.row_of || !p.s.data) return hipErrorInvalidValue;
     hipLaunchKernelGGL(join_pm_kernel, dim3(p.batch), dim3(kJoinPmThreads), 0, stream, p);
+    return hipGetLastError();
+}
+
+// One wavefront per row of Q, a workgroup walking rows blockIdx.x, + gridDim.x, ...: lane i reads symbol i of the row as join_pm_kernel does.  A row beyond
+// kJoinMaxLen symbols is never fused, so it is not read.
+__global__ __launch_bounds__(kJoinPmThreads) void join_bad_kernel(const JoinBadParams p)
+{
+    const uint32_t i = threadIdx.x;
+    for (uint64_t j = blockIdx.x; j < p.m; j += gridDim.x) {
+        const uint32_t slot = p.row_slot[j];
+        const uint32_t len = p.row_len[j];
+        bool hit = false;
+        if (len <= kJoinMaxLen && i < len && slot < p.n_slots) {
+            const uint32_t t = take_tile_of(slot);
+            uint64_t base;
+            if (p.s.tiles)
+                base = p.s.tiles[t].data_off;
+            else
+                base = take_uniform_base(t, p.s.uniform_len);
+            hit = p.bad[p.s.data[take_byte_at(base, take_lane_of(slot), i)]] != 0;
+        }
+        const uint64_t any = __ballot(hit);
+        if (i == 0) p.flags[j] = any ? 1u : 0u;
+    }
+}
+
+hipError_t launch_join_bad(const JoinBadParams& p, hipStream_t stream)
+{
+    if (p.m == 0) return hipSuccess;
+    if (!p.row_slot || !p.row_len || !p.bad || !p.flags || !p.s.data) return hipErrorInvalidValue;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(p.m, (uint64_t)std::max(1, scan_max_grid()) * 32);
+    hipLaunchKernelGGL(join_bad_kernel, dim3(grid), dim3(kJoinPmThreads), 0, stream, p);
     return hipGetLastError();
 }
 
